@@ -8,7 +8,10 @@ Authenticator.VerifyMessageAuthenTag(ClientAuthen, 0, msg, tag) checks for a
 msg = AuthenBytes(REQUEST) = "REQUEST" || seq_be64 || SHA256(op) (47 B,
 messages/authen.go:33,54-56), digest = msg || SHA256("") so e = msg[0:32],
 tag = DER(r, s) decoded to (r, s).  Operations come from a seeded PCG64;
-signatures from the library's GPU signer (deterministic nonces).
+signatures from the library's GPU signer (deterministic nonces).  Every 97th
+item of the batch is then altered (reject_mix: a flipped byte of e, s = N,
+r = 0, which reject, or s replaced by N - s, which Go accepts), so the
+statuses a step returns hold accepts and rejects at known places.
 
 One step = one pass of the hot path over one batch with inputs resident in
 HBM: the batched s^-1 kernels + the verify kernel
@@ -20,13 +23,21 @@ that batch i+1's s^-1 kernels and verify kernel overlap batch i's (DESIGN.md
 synchronize; time = max over ranks; value = all ranks' verifies / time (weak
 scaling: each rank verifies its own batch, no data-path collective).
 
-Extra fields: `roofline` for k_verify (launch duration from HIP events in the
-library, on the stream the kernel runs on, one batch at a time; plus the
-steady-state figure on ms_per_step), `sha256_stage` (the GPU SHA-256 stage
-that builds the REQUEST digests), `cpu_baseline` (the C restatement in
-oracle/ over a bounded sample on this host, rank 0 only), p50 latencies.
+A plain run does that and no more: tables and inputs, the correctness gates
+of the timed path, W + K steps, one JSON line (`value`, `ms_per_step`, ...).
+--dump-outputs DIR also writes what the last timed step returned (the batch's
+statuses: 0 accept, 1 reject) as DIR/statuses.npy; the inputs are seeded, so
+two builds can be compared output for output.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+With --full the run goes on to every other line and writes them to the
+detail file (--detail-out): `roofline` for k_verify (launch duration from HIP
+events in the library, on the stream the kernel runs on, one batch at a time;
+plus the steady-state figure on ms_per_step), `sha256_stage` (the GPU SHA-256
+stage that builds the REQUEST digests), `cpu_baseline` (the C restatement in
+oracle/ over a bounded sample on this host, rank 0 only), p50 latencies,
+single calls, adversarial input, C3, the Go wiring and binding configurations.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -104,6 +115,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--batch", type=int, default=1 << 20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other line (SHA-256 stage, roofline, "
+                         "latencies, single calls, adversarial, C3, Go wiring, binding configurations, CPU "
+                         "baselines) and write the detail file; the options below --streams shape those lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the batch's statuses) as DIR/<name>.npy")
     ap.add_argument("--g-window", type=int, default=29,
                     help="generator comb window in bits (4..29; HBM cost in include/minbft_gpu.h)")
     ap.add_argument("--q-window", type=int, default=29,
@@ -186,6 +203,30 @@ def sha256_stage(auth, torch, dev, st, ops: np.ndarray, seqs: np.ndarray, e_ref,
 
 
 N_ORDER = 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551
+
+
+def reject_mix(torch, dev, d_e, d_r, d_s, B: int):
+    """Copies of (e, r, s) with every 97th item altered (kind cycling 0..3):
+    0 flips a byte of e, 1 sets s = N, 2 sets r = 0 (all must reject), 3
+    replaces s by N - s (high s: Go has no low-s rule, must accept); every
+    other item must accept.  Returns (e2, r2, s2, want, counts): want = the
+    status of every item by construction."""
+    idx = torch.arange(0, B, 97, device=dev)
+    kind = (idx // 97) % 4
+    e2, r2, s2 = d_e.clone(), d_r.clone(), d_s.clone()
+    i0, i1, i2, i3 = (idx[kind == k] for k in range(4))
+    e2[i0, 11] ^= 0x40
+    s2[i1] = torch.tensor(list(N_ORDER.to_bytes(32, "big")), dtype=torch.uint8, device=dev)
+    r2[i2] = 0
+    hs = s2[i3].cpu().numpy()
+    for k in range(hs.shape[0]):
+        hs[k] = np.frombuffer((N_ORDER - int.from_bytes(hs[k].tobytes(), "big")).to_bytes(32, "big"),
+                              dtype=np.uint8)
+    s2[i3] = torch.from_numpy(hs).to(dev)
+    want = torch.zeros((B,), dtype=torch.uint8, device=dev)
+    want[torch.cat([i0, i1, i2])] = 1
+    return e2, r2, s2, want, {"altered": int(idx.numel()), "rejects": int(i0.numel() + i1.numel() + i2.numel()),
+                              "high_s_accepts": int(i3.numel())}
 
 
 def reject_gate(auth, torch, dev, d_e, d_r, d_s, d_slot, B: int, st):
@@ -1770,9 +1811,10 @@ def compact_line(full: dict, detail_file) -> dict:
             "scaling", "vs_baseline", "dtype", "data", "config", "p50_batch_latency_ms",
             "p50_batch_latency_device_ms", "kernel_ms", "sha256_stage")
     line = {k: full[k] for k in keep if k in full}
-    line["p50_batch_latency_definition"] = ("host submit -> statuses back, 1M VerifyMessageAuthenTag calls "
-                                            "through mbft_verify_batch_flat32 (the Go binding's form), median of "
-                                            "latency_reps after 3 warm-ups")
+    if "p50_batch_latency_ms" in line:
+        line["p50_batch_latency_definition"] = ("host submit -> statuses back, 1M VerifyMessageAuthenTag calls "
+                                                "through mbft_verify_batch_flat32 (the Go binding's form), median "
+                                                "of latency_reps after 3 warm-ups")
     roof = full.get("roofline")
     if roof:
         line["roofline"] = {k: roof.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic",
@@ -1815,6 +1857,27 @@ def write_detail(full: dict, path: str):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, rank: int, arrays: dict):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32 (ranks
+    past 0 add _rank<r> to the name).  The arrays share DUMP_LIMIT_BYTES
+    evenly; a larger one is cut to a sorted sample of its first axis drawn
+    from a fixed seed, so two runs keep the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        row_bytes = 4 * max(int(np.prod(a.shape[1:])), 1)
+        if a.shape[0] * row_bytes > share:
+            keep = np.random.Generator(np.random.PCG64(0xD0)).choice(a.shape[0], size=share // row_bytes,
+                                                                    replace=False)
+            a = a[np.sort(keep)]
+        suffix = f"_rank{rank}" if rank else ""
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.astype(np.float32))
+
+
 def main():
     args = parse()
     from minbft_amd import dist as mdist
@@ -1830,7 +1893,7 @@ def main():
     world, rank, local = mdist.env_ranks()
     # the microbenchmark runs as a child program BEFORE this process
     # initializes the GPU
-    peak = measure_peak_mad_rate(run=not args.no_peak_run) if rank == 0 else None
+    peak = measure_peak_mad_rate(run=not args.no_peak_run) if rank == 0 and args.full else None
     use_dist = world > 1 or args.force_dist
     if use_dist:
         # RCCL prints a version banner on stdout at communicator creation;
@@ -1870,7 +1933,7 @@ def main():
         e = np.ascontiguousarray(msgs[:, :32])  # quirk: e = (msg || SHA256(""))[0:32]
         d_priv = torch.from_numpy(priv).to(dev)
         d_e = torch.from_numpy(e).to(dev)
-        sha = sha256_stage(auth, torch, dev, streams[0], ops, seqs, d_e)
+        sha = sha256_stage(auth, torch, dev, streams[0], ops, seqs, d_e) if args.full else None
         del ops
         d_r = torch.empty((B, 32), dtype=torch.uint8, device=dev)
         d_s = torch.empty((B, 32), dtype=torch.uint8, device=dev)
@@ -1896,28 +1959,34 @@ def main():
         d_sts = [torch.empty((B,), dtype=torch.uint8, device=dev) for _ in streams]
         d_st = d_sts[0]
         nstep = [0]
+        # The timed batch: the valid batch with the reject mix in it (about
+        # 1 item in 100 altered), so that the statuses a step returns say
+        # something: t_want holds every item's status by construction.
+        t_e, t_r, t_s, t_want, _ = reject_mix(torch, dev, d_e, d_r, d_s, B)
 
         def step():
             k = nstep[0] % len(streams)
             nstep[0] += 1
-            auth.verify_prehashed_device(d_e.data_ptr(), d_r.data_ptr(), d_s.data_ptr(),
+            auth.verify_prehashed_device(t_e.data_ptr(), t_r.data_ptr(), t_s.data_ptr(),
                                          d_slot.data_ptr(), B, d_sts[k].data_ptr(),
                                          streams[k].cuda_stream)
 
-        # correctness gate at the benchmarked windows: the valid batch is
-        # accepted in full on every stream, and a reject mix (every 97th item:
-        # flipped e byte, s = N, r = 0, or high s -- which Go accepts) comes
-        # back exactly as constructed
+        # correctness gate at the benchmarked windows: the timed batch (the
+        # valid batch with the reject mix -- every 97th item: flipped e byte,
+        # s = N, r = 0, or high s, which Go accepts) comes back exactly as
+        # constructed on every stream, and so does the mix built and run once
+        # more on its own (reject_gate)
         for _ in streams:
             step()
         torch.cuda.synchronize()
-        n_acc = min(int((d == 0).sum().item()) for d in d_sts)
-        if n_acc != B:
-            raise SystemExit(f"bench correctness gate failed: {n_acc}/{B} accepted")
+        n_diff = max(int((d != t_want).sum().item()) for d in d_sts)
+        if n_diff:
+            raise SystemExit(f"bench correctness gate failed: {n_diff}/{B} statuses differ from the construction")
         gate = reject_gate(auth, torch, dev, d_e, d_r, d_s, d_slot, B, streams[0])
         # The sustained gate: --gate-batches more batches back to back over
         # the streams, every status vector checked on the device (a count of
-        # non-accepts per stream, enqueued behind each batch on its stream:
+        # statuses that differ from the construction, per stream, enqueued
+        # behind each batch on its stream:
         # no host synchronize between batches).  It ends right before the W
         # warm-up steps, so they and the K timed steps start from the clock
         # of sustained load: from an idle GPU the first ~20 ms of batches run
@@ -1928,11 +1997,11 @@ def main():
             k = nstep[0] % len(streams)
             step()
             with torch.cuda.stream(streams[k]):
-                bads[k] += (d_sts[k] != 0).sum()
+                bads[k] += (d_sts[k] != t_want).sum()
         torch.cuda.synchronize()
         n_bad = sum(int(b.item()) for b in bads)
         if n_bad:
-            raise SystemExit(f"bench sustained gate failed: {n_bad} statuses not accepted")
+            raise SystemExit(f"bench sustained gate failed: {n_bad} statuses differ from the construction")
         gate["sustained_batches_checked"] = args.gate_batches
 
         for _ in range(args.warmup):
@@ -1953,6 +2022,50 @@ def main():
         auth.profile(False)
         dt = t1 - t0
         dt = mdist.max_over_ranks(dist, dt, dev)  # MAX over ranks (no-op at N=1)
+        if args.dump_outputs:
+            # what the caller of the last timed step got back: that batch's
+            # statuses (the stream it ran on is the last one used)
+            last = (nstep[0] - 1) % len(streams)
+            dump_outputs(args.dump_outputs, rank, {"statuses": d_sts[last].cpu().numpy()})
+        head = {
+            "metric": "ECDSA-P256 verifies/sec at batch 1M (1/2/4/8 GPU); p50 batch latency",
+            "value": world * B * args.steps / dt,
+            "unit": "verifies/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32 (29-bit-limb mod-p/mod-N integer arithmetic)",
+            "data": "synthetic: seeded 256-byte REQUEST ops, GPU-signed (deterministic nonce)",
+            "config": {"workload": "C2: 1M single-signer REQUEST ECDSA-P256 verify batch per GPU "
+                                   "(Authenticator ClientAuthen, Sum(m) digest), inputs resident in HBM",
+                       "batch_per_gpu": B, "parallelism": f"independent shards x{world}",
+                       "comb_windows": {"G": args.g_window, "Q": args.q_window},
+                       "batches_in_flight": len(streams),
+                       "reject_mix": "every 97th item altered (flipped e byte, s = N, r = 0: reject; "
+                                     "N - s: accept), so a step's statuses are not all zero"},
+            "table_build_s": t_tab,
+            "table_build_basis": f"generator (W = {args.g_window}) + key (W = {args.q_window}) comb tables "
+                                 f"only: {t_tab - t_key:.2f} s + {t_key:.2f} s",
+            "inputs_s": t_inp,
+        }
+        if not args.full:
+            # the plain run ends here: the headline alone (every other line
+            # is behind --full)
+            result = None
+            if rank == 0:
+                nb = max(prof["batches"], 1)
+                result = {**head, "gate": gate,
+                          "kernel_ms": {"k_verify_in_timed_loop_overlapped": prof["verify_ms"] / nb,
+                                        "batched_inverse_span_overlapped": prof["inverse_ms"] / nb}}
+                print(json.dumps(compact_line(result, None)), flush=True)
+            if use_dist:
+                dist.barrier()
+                dist.destroy_process_group()
+            return result
 
         # per-step device latency (synchronized), p50
         # one batch at a time (synchronized): p50 batch latency, and the
@@ -2068,7 +2181,6 @@ def main():
 
         result = None
         if rank == 0:
-            value = world * B * args.steps / dt
             # k_verify launches in the timed loop overlap the next batch's
             # launch (two caller streams): their event-bracketed duration is
             # longer than the kernel's own.  The roofline uses the isolated
@@ -2097,27 +2209,7 @@ def main():
             p50_items = float(np.median(lat_auth))
             p50_auth = float(np.median(lat_flat))
             result = {
-                "metric": "ECDSA-P256 verifies/sec at batch 1M (1/2/4/8 GPU); p50 batch latency",
-                "value": value,
-                "unit": "verifies/s",
-                "n_gpus": world,
-                "steps": args.steps,
-                "warmup": args.warmup,
-                "ms_per_step": dt / args.steps * 1e3,
-                "higher_is_better": True,
-                "scaling": "weak",
-                "vs_baseline": None,
-                "dtype": "u32 (29-bit-limb mod-p/mod-N integer arithmetic)",
-                "data": "synthetic: seeded 256-byte REQUEST ops, GPU-signed (deterministic nonce)",
-                "config": {"workload": "C2: 1M single-signer REQUEST ECDSA-P256 verify batch per GPU "
-                                       "(Authenticator ClientAuthen, Sum(m) digest), inputs resident in HBM",
-                           "batch_per_gpu": B, "parallelism": f"independent shards x{world}",
-                           "comb_windows": {"G": args.g_window, "Q": args.q_window},
-                           "batches_in_flight": len(streams)},
-                "table_build_s": t_tab,
-                "table_build_basis": f"generator (W = {args.g_window}) + key (W = {args.q_window}) comb tables "
-                                     f"only: {t_tab - t_key:.2f} s + {t_key:.2f} s",
-                "inputs_s": t_inp,
+                **head,
                 "p50_batch_latency_ms": p50_auth * 1e3,
                 "p50_batch_latency_definition": "host submit -> statuses back for 1M VerifyMessageAuthenTag "
                                                 "calls through mbft_verify_batch_flat32 as the Go binding calls "

@@ -14,6 +14,7 @@ as text).  Fails on any drift:
   marshal (go/gpuauth/messages.go), and the header's field order matches the
   Python dtype the tests use (minbft_amd/_lib.py).
 """
+import json
 import os
 import re
 
@@ -71,14 +72,13 @@ def test_stage_codes():
 
 def test_roles_and_role_byte():
     hdr = _enum(_read("include", "minbft_gpu.h"), "mbft_role")
-    ref = os.path.join("/root/reference", "api", "api.go")
-    # the reference (study only; absent on the GPU box): 1 + iota in this order
-    if os.path.exists(ref):
-        with open(ref) as f:
-            txt = f.read()
-        block = re.search(r"ReplicaAuthen AuthenticationRole = 1 \+ iota(.*?)\n\)", txt, re.S).group(1)
-        order = ["ReplicaAuthen"] + re.findall(r"^\s*(USIGAuthen|ClientAuthen)\s*$", block, re.M)
-        assert order == ["ReplicaAuthen", "USIGAuthen", "ClientAuthen"]
+    # the reference's role names in declaration order (1 + iota), recorded in
+    # tests/golden/reference_roles.json
+    ref = json.loads(_read("tests", "golden", "reference_roles.json"))
+    assert ref["names"] == ["ReplicaAuthen", "USIGAuthen", "ClientAuthen"]
+    value = {nm: ref["first_value"] + i for i, nm in enumerate(ref["names"])}
+    assert hdr == {"MBFT_ROLE_REPLICA": value["ReplicaAuthen"], "MBFT_ROLE_USIG": value["USIGAuthen"],
+                   "MBFT_ROLE_CLIENT": value["ClientAuthen"]}
     assert hdr == {"MBFT_ROLE_REPLICA": 1, "MBFT_ROLE_USIG": 2, "MBFT_ROLE_CLIENT": 3}
     go = _read("go", "gpuauth", "gpuauth.go")
     fn = re.search(r"func roleByte\(r api\.AuthenticationRole\) byte \{(.*?)\n\}", go, re.S)
