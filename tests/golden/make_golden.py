@@ -16,6 +16,10 @@ Fixtures:
                   accumulator collisions (doubling / infinity mid-way) of
                   the GPU's 8-bit fixed-window comb.
   comb_windows.json  accumulator collisions for the 20..29-bit key windows.
+  scalar_edges.json  crafted (u1, u2) at the corners of the comb's signed-
+                  digit recoding: the top window's last entry (digit 2^L),
+                  the largest positive digit 2^(W-1), a zero digit that
+                  still carries, small scalars.
   der.json        DER signature strings -> Go encoding/asn1 outcome.
   authen.json     Authenticator-level call sequences (ECDSA roles with the
                   Sum(m) quirk, USIG roles with epoch capture), with the
@@ -256,6 +260,73 @@ def make_comb_windows():
                 q, e, r, s = comb_collision(i, inf, W, rng)
                 lab = ("comb%d_inf_w%d" if inf else "comb%d_dbl_w%d") % (W, i)
                 out.append(vec(q, e, r, s, lab))
+    return out
+
+
+def scalar_edge_values(rng):
+    """The edge scalars of scalar_edges.json, as (name, u), each checked for
+    the digit property it is named for under signed_digits."""
+    rep = lambda pat, k: int.from_bytes(bytes.fromhex(pat) * k, "big")  # noqa: E731
+    edges = [
+        ("top_rnd", o.N - 1 - rng.randrange(1 << 200)),
+        ("top_Nm1", o.N - 1),
+        ("half8", rep("80", 32)),
+        ("half16", rep("8000", 16)),
+        ("ones_carry", (1 << 255) - 1),
+        ("b81", rep("81", 32)),
+        ("b7f", rep("7f", 32)),
+        ("one", 1),
+        ("two", 2),
+    ]
+    u = dict(edges)
+    for W in range(4, 30):
+        S = -(-256 // W)
+        L = 256 - (S - 1) * W
+        for name in ("top_rnd", "top_Nm1"):
+            # the recoding carries into the top window: the table's last entry
+            assert signed_digits(u[name], W)[-1] == 1 << L, (name, W)
+    assert signed_digits(u["half8"], 8) == [128] * 32
+    assert signed_digits(u["half16"], 16) == [1 << 15] * 16
+    assert signed_digits(u["half16"], 8) == [0, 128] * 16
+    for W in (8, 16):
+        # windows of all ones plus a carry: digit 0, and the carry goes on
+        S = 256 // W
+        assert signed_digits(u["ones_carry"], W) == [-1] + [0] * (S - 2) + [1 << (W - 1)]
+    assert signed_digits(u["b81"], 8) == [-127] + [-126] * 30 + [130]
+    assert signed_digits(u["b7f"], 8) == [127] * 32
+    for W in range(4, 30):
+        S = -(-256 // W)
+        assert signed_digits(u["one"], W) == [1] + [0] * (S - 1)
+        assert signed_digits(u["two"], W) == [2] + [0] * (S - 1)
+    assert all(0 < v < o.N for v in u.values())
+    return edges
+
+
+def make_scalar_edges():
+    """Accepting signatures crafted from chosen (u1, u2) under one key with a
+    known private scalar (R = u1 G + u2 Q, r = R.x mod N, s = r / u2,
+    e = u1 s), each followed by the same with e ^ 1 (reject): every edge
+    scalar as u1 beside a random u2, as u2 beside a random u1, and as both.
+    Own RNG stream so that the other fixtures are unchanged."""
+    rng = random.Random(0x45444745)  # "EDGE"
+    d = key_from_seed(0)
+    q = o.pubkey(d)
+    out = []
+    for name, u in scalar_edge_values(rng):
+        for lab, u1, u2 in [("u1_" + name, u, rng.randrange(1, o.N)),
+                            ("u2_" + name, rng.randrange(1, o.N), u),
+                            ("both_" + name, u, u)]:
+            R = o.scalar_mult((u1 + u2 * d) % o.N, o.G)
+            assert R is not None and R == o.combined_mult(u1, u2, q)
+            r = R[0] % o.N
+            assert r != 0, lab
+            s = r * pow(u2, -1, o.N) % o.N
+            e = u1 * s % o.N
+            assert e * pow(s, -1, o.N) % o.N == u1 and r * pow(s, -1, o.N) % o.N == u2
+            out.append(vec(q, e, r, s, lab))
+            out.append(vec(q, e ^ 1, r, s, lab + "_tampered"))
+            assert (out[-2]["expect"], out[-1]["expect"]) == (1, 0), lab
+    assert len(out) == 54
     return out
 
 
@@ -584,6 +655,7 @@ def main():
     dump("kat.json", make_kat())
     dump("prehashed.json", make_prehashed())
     dump("comb_windows.json", make_comb_windows())
+    dump("scalar_edges.json", make_scalar_edges())
     dump("der.json", make_der())
     a = make_authen()
     expected_authen(a)

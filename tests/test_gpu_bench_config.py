@@ -10,6 +10,8 @@ gets the context to itself in turn (mbft_clear_keys between keys):
   which at W = 29 are ordinary vectors), under its own key at W = 29;
 * the comb29 accumulator-collision vectors (tests/golden/comb_windows.json,
   built for the signed 29-bit key windows by make_golden.py);
+* the recoding-corner vectors (tests/golden/scalar_edges.json): scalars that
+  reach the last entry of the top window, under their one key;
 * a full 1,048,576-item batch, as bench.py runs it, with a reject mix every
   97th item (tampered e, r, s; r = 0; s = N; a wrong key registered at
   W = 8 beside the W = 29 key; high-s, which Go accepts): every status
@@ -71,6 +73,18 @@ def test_comb29_collisions_w29(auth29):
     assert len(sel) >= 5
     _check(_run_per_key(auth29, xy[sel], e[sel], r[sel], s[sel]), exp[sel],
            [labels[i] for i in sel])
+
+
+def test_scalar_edges_w29(auth29):
+    """The recoding corners at the measured configuration (G = 29 / Q = 29,
+    one key, one 129 GiB table): u1 / u2 in [N - 2^200, N) carry into the top
+    window and read the last entry (digit 2^24) of both tables, which no
+    random scalar reaches; with the half-window, all-ones-plus-carry and small
+    scalars of tests/golden/scalar_edges.json.  A table one entry short, or a
+    recoding that drops the top carry, rejects an accepting vector."""
+    xy, e, r, s, exp, labels = prehashed_arrays("scalar_edges.json")
+    assert (xy == xy[0]).all() and exp.sum() == 27
+    _check(_run_per_key(auth29, xy, e, r, s), exp, labels)
 
 
 def test_full_batch_w29_mix(auth29):

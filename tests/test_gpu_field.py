@@ -9,7 +9,14 @@ madd in the comb-table build produced 3 wrong entries of one key's table;
 found by tests/test_gpu_configs.py::test_c4_adversarial_gpu_share).
 
 Also a library-level regression: that key's table entries (window 0, digits
-30855, 61710, 61711 at W = 16) are hit by crafted valid signatures."""
+30855, 61710, 61711 at W = 16) are hit by crafted valid signatures.
+
+The second half covers what runs only on the device and was checked only
+through accept / reject statuses: the mod-N arithmetic and u1 / u2
+(scalars), the comb's signed recoding, the whole-wave inversion mod N
+(scalar_dev.h), the joins of two Chudnovsky points and their wave-uniform
+forms (ecc.h), and the accept test x_matches_r -- each at the documented
+input bounds, with non-canonical representatives."""
 import ctypes
 import hashlib
 import os
@@ -386,3 +393,383 @@ def test_chudnovsky_lazy_and_last(harness):
     vals = [rng.randrange(1 << 258) for _ in range(400)]
     res = run(harness, [("norm_lazy", [lazy_limbs(v, rng), 0, 0, 0, 0, 0]) for v in vals])
     assert all(value(r[0]) == v and normalized(r[0]) for v, r in zip(vals, res))
+
+
+# ---------------------------------------------------------------------------
+# The verifier's scalar side (scalar_dev.h), the joins of partial sums and the
+# accept test: mod-N arithmetic, u1 / u2, the comb's recoding, the whole-wave
+# inversion, ec_add_chud_x / _full, the wave-uniform forms, x_matches_r.
+N = 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551
+RNINV = pow(R, -1, N)
+GROUP_OPS = {"add_full": 0, "add_x_same": 1, "add_x_diff": 2, "madd_p": 3, "madd_n": 4,
+             "aff_p": 5, "aff_n": 6}
+FN_OPS = {"fn_mul": 32, "fn_canon": 33, "fn_csub1": 34, "fn_to_mont": 35, "fn_from_mont": 36,
+          "scalars": 37, "x_matches": 38}
+OPS.update(FN_OPS)
+
+
+@pytest.fixture(scope="module")
+def harness2(harness):
+    h = harness
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    h.comb_check_run.argtypes = [vp, vp, i]
+    h.modinv_wave_check_run.argtypes = [vp, vp, i]
+    h.group_check_run.argtypes = [vp, vp, vp, i, i]
+    for f in (h.comb_check_run, h.modinv_wave_check_run, h.group_check_run):
+        f.restype = i
+    return h
+
+
+def words(v):
+    """8 LE words of v < 2^256, in a 9-limb slot (raw, not limbs)."""
+    assert 0 <= v < (1 << 256)
+    return [(v >> (32 * k)) & 0xFFFFFFFF for k in range(8)] + [0]
+
+
+def from_words(w):
+    return sum(int(x) << (32 * k) for k, x in enumerate(w[:8]))
+
+
+def push_up(v, mod, bound, rng, pick=None):
+    """A representative of v (mod `mod`) below `bound`: the value itself, the
+    largest one, or a random one."""
+    top = (bound - 1 - v) // mod
+    pick = rng.randrange(3) if pick is None else pick
+    return v + mod * (top if pick == 0 else (rng.randrange(top + 1) if pick == 1 else 0))
+
+
+def golden_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "make_golden", os.path.join(ROOT, "tests", "golden", "make_golden.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_mod_n_ops(harness2):
+    """fn_mul, fn_canon, fn_csub, fn_to_mont, fn_from_mont (fe29.h) run only
+    on the device.  fn_mul on inputs up to 2^259 (adversarial limb patterns):
+    value mod N, the documented bound a b / 2^261 + N and normalized limbs --
+    a bound that fails makes the next fn_csub leave a non-canonical u.
+    fn_canon at every multiple of N it must remove (k N - 1, k N, k N + 1,
+    k = 0..4, and 2^258 - 1): exactly v mod N.  fn_csub(., 1) below 2N."""
+    rng = random.Random(0xF0D)
+    cases = []
+    for _ in range(3000):
+        cases.append(("fn_mul", [rnd_value(rng, 1 << 259), rnd_value(rng, 1 << 259)]))
+        cases.append(("fn_canon", [rnd_value(rng, 1 << 258)]))
+        cases.append(("fn_csub1", [rnd_value(rng, 2 * N)]))
+        cases.append(("fn_to_mont", [rnd_value(rng, 1 << 256)]))
+        cases.append(("fn_from_mont", [rnd_value(rng, 1 << 258)]))
+    top = (1 << 259) - 1
+    cases += [("fn_mul", [top, top]), ("fn_mul", [top, 0]), ("fn_mul", [N - 1, N - 1]),
+              ("fn_mul", [(1 << 258) - 1, (1 << 256) - 1])]
+    for k in range(5):
+        cases += [("fn_canon", [k * N + d]) for d in (-1, 0, 1) if k * N + d >= 0]
+    cases += [("fn_canon", [(1 << 258) - 1]), ("fn_canon", [(1 << 258) - (1 << 232)])]
+    cases += [("fn_csub1", [v]) for v in (0, 1, N - 1, N, N + 1, 2 * N - 1)]
+    cases += [("fn_to_mont", [v]) for v in (0, 1, N - 1, N, (1 << 256) - 1)]
+    cases += [("fn_from_mont", [v]) for v in (0, 1, N - 1, N, (1 << 258) - 1)]
+    res = run(harness2, cases)
+    bad = []
+    for (op, vals), (o0, _, _, _) in zip(cases, res):
+        v, a = value(o0), vals[0]
+        if op == "fn_mul":
+            ok = v % N == a * vals[1] * RNINV % N and v < a * vals[1] // R + N + 1
+        elif op == "fn_canon":
+            ok = v == a % N
+        elif op == "fn_csub1":
+            ok = v == (a - N if a >= N else a)
+        elif op == "fn_to_mont":
+            ok = v % N == a * R % N and v < (1 << 258)
+        else:
+            ok = v % N == a * RNINV % N and v < a // R + N + 1
+        if not (ok and normalized(o0)):
+            bad.append((op, [hex(x) for x in vals], hex(v)))
+    assert not bad, (len(bad), bad[:5])
+
+
+def test_scalars_canonical(harness2):
+    """scalars() (u1 = e w, u2 = r w): e and r anywhere below 2^256 (0, N - 1,
+    N, 2^256 - 1 among them: Go reduces e, and r + N enters elsewhere), w ANY
+    representative below 2^258 of a Montgomery-form value, the bound the
+    single conditional subtraction rests on.  Both outputs exactly
+    e w 2^-261 mod N as canonical words: a non-canonical u (u + N) recodes
+    into other comb digits and rejects a valid signature on the GPU alone."""
+    rng = random.Random(0x5CA1)
+    fixed = [0, 1, N - 1, N, N + 1, (1 << 256) - 1, 1 << 255]
+    cases = []
+    for i in range(3000):
+        e = fixed[i % 7] if i % 5 == 0 else rnd_value(rng, 1 << 256)
+        r = fixed[(i // 7) % 7] if i % 3 == 0 else rnd_value(rng, 1 << 256)
+        w = push_up(rng.randrange(N) * R % N, N, 1 << 258, rng, pick=i % 3)
+        cases.append(("scalars", [e, r, w]))
+    wmax = push_up(rng.randrange(N), N, 1 << 258, rng, pick=0)   # the largest representative
+    assert (1 << 258) - N <= wmax < (1 << 258)
+    cases += [("scalars", [(1 << 256) - 1, (1 << 256) - 1, (1 << 258) - 1]),
+              ("scalars", [(1 << 256) - 1, N - 1, wmax]), ("scalars", [0, 0, (1 << 258) - 1])]
+    res = run(harness2, cases)
+    bad = []
+    for (_, (e, r, w)), (o0, o1, _, _) in zip(cases, res):
+        assert w < (1 << 258)
+        u1, u2 = from_words(o0), from_words(o1)
+        if u1 != e * w * RNINV % N or u2 != r * w * RNINV % N:
+            bad.append((hex(e), hex(r), hex(w), hex(u1), hex(u2)))
+    assert not bad, (len(bad), bad[:5])
+
+
+def test_comb_recoding(harness2):
+    """comb_digit / shr_words over whole scalars at every window 4..29: the
+    loop every verify form runs, against make_golden.signed_digits.  The
+    scalars include the recoding's corners (tests/golden/scalar_edges.json's
+    u: a carry into the top window -> digit 2^L, the table's last entry; a
+    window exactly 2^(W-1); all ones plus a carry -> a zero digit that still
+    carries).  Every index must lie inside its window's entry count: one
+    past it reads the next window's (or the next key's) first entry."""
+    mg = golden_module()
+    rng = random.Random(0xD161)
+    us = [u for _, u in mg.scalar_edge_values(random.Random(0x45444745))]
+    us += [0, N - 2, (1 << 256) - 1, 1 << 255, (1 << 255) + 1, N - (1 << 200)]
+    us += [rng.randrange(1 << 256) for _ in range(24)]
+    us += [rnd_value(rng, 1 << 256) for _ in range(8)]
+    cases = [(u, W) for u in us for W in range(4, 30)]
+    inp = np.array([words(u)[:8] + [W] for u, W in cases], dtype=np.uint32)
+    out = np.zeros((len(cases), 64), dtype=np.uint32)
+    assert harness2.comb_check_run(inp.ctypes.data, out.ctypes.data, len(cases)) == 0
+    bad = []
+    for (u, W), row in zip(cases, out.tolist()):
+        dig = mg.signed_digits(u, W)
+        S = len(dig)
+        L = 256 - (S - 1) * W
+        want = []
+        for k, d in enumerate(dig):
+            assert abs(d) <= (1 << (L if k == S - 1 else W - 1))
+            want.append((0 if d == 0 else abs(d) - 1) | (1 << 30 if d < 0 else 0) | (1 << 31 if d == 0 else 0))
+        # (a zero digit's sign is not read: all ones plus a carry reports it
+        # negative, since that is what carries)
+        got = [x & ~(1 << 30) if x >> 31 else x for x in row[:S]]
+        if got != want or any(x != 0xFFFFFFFF for x in row[S:]):
+            bad.append((hex(u), W))
+    assert not bad, (len(bad), bad[:5])
+    # the named corners are present
+    assert any(mg.signed_digits(u, 29)[-1] == 1 << 24 for u in us)
+    assert any(0 in mg.signed_digits(u, 8)[1:-1] and u == (1 << 255) - 1 for u in us)
+
+
+def test_modinv_wave(harness2):
+    """modinv_n_var_wave (the roots of the batched s^-1, one value per wave,
+    the 2x2 matrix split over lane quads with DPP broadcasts): every one of
+    the 64 lanes returns pow(x, -1, N) and true; 0 returns false.  A lane
+    quad out of step would hand one lane another lane's half of the update."""
+    rng = random.Random(0x1A7E)
+    xs = [1, 2, 3, N - 1, N - 2, (N + 1) // 2, (N - 1) // 2] + [1 << k for k in range(1, 256, 15)] + \
+         [1 << 255, (1 << 255) - 1] + [rng.randrange(1, N) for _ in range(40)] + \
+         [rnd_value(rng, N) or 1 for _ in range(8)]
+    xs.append(0)
+    inp = np.array([words(x)[:8] for x in xs], dtype=np.uint32)
+    out = np.zeros((len(xs), 64, 9), dtype=np.uint32)
+    assert harness2.modinv_wave_check_run(inp.ctypes.data, out.ctypes.data, len(xs)) == 0
+    bad = []
+    for x, lanes in zip(xs, out):
+        assert (lanes == lanes[0]).all(), hex(x)
+        got, ok = from_words(lanes[0]), int(lanes[0][8])
+        if x == 0:
+            if ok != 0:
+                bad.append((hex(x), ok))
+        elif ok != 1 or got != pow(x, -1, N):
+            bad.append((hex(x), ok, hex(got)))
+    assert not bad, bad[:5]
+
+
+def run_group(h, cases, wide):
+    """cases: (op, [8 values or limb lists]) -> per case (wide: per case and
+    lane) the 37 output words."""
+    n = len(cases)
+    op = np.array([GROUP_OPS[c[0]] for c in cases], dtype=np.uint32)
+    inp = np.zeros((n, 72), dtype=np.uint32)
+    for i, (_, vals) in enumerate(cases):
+        for k, v in enumerate(vals):
+            inp[i, 9 * k: 9 * k + 9] = v if isinstance(v, list) else limbs(v)
+    out = np.zeros((n, 64, 37) if wide else (n, 37), dtype=np.uint32)
+    assert h.group_check_run(op.ctypes.data, inp.ctypes.data, out.ctypes.data, n, 1 if wide else 0) == 0
+    return out
+
+
+CHUD_LIM = [SUB2X_OUT, 1 << 258, 1 << 258, 1 << 258]
+
+
+def chud_rep(pt, z, rng, yneg=False, pick=None):
+    """(X, Y, ZZ, ZZZ) of the affine point with Z = z, Montgomery form, each
+    coordinate a representative up to the bound the joins take as inputs
+    (X < 2^257 + 2^234, the others < 2^258); yneg: Y holds -Y."""
+    y = (P - pt[1]) % P if yneg else pt[1]
+    m = [pt[0] * z * z % P, y * z * z * z % P, z * z % P, z * z * z % P]
+    return [push_up(v * R % P, P, lim, rng, pick) for v, lim in zip(m, CHUD_LIM)]
+
+
+def other_point(pts, p1, rng):
+    while True:
+        p2 = pts[rng.randrange(len(pts))]
+        if p2[0] != p1[0]:
+            return p2
+
+
+def test_chud_joins(harness2):
+    """ec_add_chud_full (k_verify_split's joins of partial comb sums, TRUE Y)
+    and ec_add_chud_x (k_verify_pairs' x-only join, Y under the caller's sign
+    convention, both same_sign values) on two Chudnovsky points whose
+    coordinates are non-canonical representatives up to their documented
+    bounds -- where the fold of fe_sub once went negative.  The affine result
+    against big-integer addition; for the full form the true Y and
+    ZZ^3 == ZZZ^2; outputs inside the bounds the next join level takes as
+    inputs; true returned.  b = a and b = -a under another Z return false
+    (the caller then takes the exact path)."""
+    from oracle import p256 as o
+    rng = random.Random(0x101A)
+    pts = [o.scalar_mult(rng.randrange(1, o.N), o.G) for _ in range(48)]
+    cases, want = [], []
+    planned = 3000
+    for i in range(planned):
+        p1 = pts[rng.randrange(48)]
+        p2 = other_point(pts, p1, rng)
+        pick = 0 if i % 4 == 0 else None
+        if i % 2 == 0:
+            a = chud_rep(p1, rng.randrange(1, P), rng, pick=pick)
+            b = chud_rep(p2, rng.randrange(1, P), rng, pick=pick)
+            cases.append(("add_full", a + b))
+        else:
+            sa, sb = rng.randrange(2) == 1, rng.randrange(2) == 1
+            a = chud_rep(p1, rng.randrange(1, P), rng, yneg=sa, pick=pick)
+            b = chud_rep(p2, rng.randrange(1, P), rng, yneg=sb, pick=pick)
+            cases.append(("add_x_same" if sa == sb else "add_x_diff", a + b))
+        want.append(o.point_add(p1, p2))
+    ndeg = 0
+    for i in range(60):   # degenerate: the same point, or its negative, under another Z
+        p1 = pts[rng.randrange(48)]
+        neg = i % 2 == 1
+        a = chud_rep(p1, rng.randrange(1, P), rng)
+        b = chud_rep(p1, rng.randrange(1, P), rng, yneg=neg)
+        cases.append((("add_full", "add_x_same", "add_x_diff")[i % 3], a + b))
+        want.append(None)
+        ndeg += 1
+    assert len(cases) == planned + ndeg
+    out = run_group(harness2, cases, wide=False)
+    bad, seen = [], {"add_full": 0, "add_x_same": 0, "add_x_diff": 0, None: 0}
+    for (op, _), w, row in zip(cases, want, out):
+        X, Y, ZZ, ZZZ, ret = row[0:9], row[9:18], row[18:27], row[27:36], int(row[36])
+        if w is None:
+            seen[None] += 1
+            if ret != 0:
+                bad.append((op, "degenerate", ret))
+            continue
+        seen[op] += 1
+        zz = value(ZZ) * RINV % P
+        ok = ret == 1 and zz != 0 and value(X) * RINV * pow(zz, -1, P) % P == w[0] and \
+            value(X) < SUB2X_OUT and value(ZZ) < (1 << 258) and normalized(X) and normalized(ZZ)
+        if ok and op == "add_full":
+            zzz = value(ZZZ) * RINV % P
+            ok = value(Y) * RINV * pow(zzz, -1, P) % P == w[1] and pow(zz, 3, P) == pow(zzz, 2, P) and \
+                value(Y) < (1 << 258) and value(ZZZ) < (1 << 258) and normalized(Y) and normalized(ZZZ)
+        if not ok:
+            bad.append((op, ret))
+    assert not bad, (len(bad), bad[:10])
+    assert sum(seen.values()) == planned + ndeg and seen["add_full"] == planned // 2 and \
+        seen["add_x_same"] > 300 and seen["add_x_diff"] > 300 and seen[None] == ndeg
+
+
+def test_wide_forms_match_sequential(harness2):
+    """ec_madd_chud_wide, ec_add_affine_chud_wide and ec_add_chud_full_wide
+    (k_verify_split: one item per wave, the products of each dependency level
+    in different 16-lane groups) against ecc.h's promise "the same results
+    bit for bit": one case per 64-lane block, every lane's outputs equal and
+    limb for limb those of the sequential form on the same inputs (which the
+    tests above pin against big integers).  A wrong operand select in one
+    lane group, or a broadcast from the wrong group's first lane, differs."""
+    from oracle import p256 as o
+    rng = random.Random(0x51DE)
+    pts = [o.scalar_mult(rng.randrange(1, o.N), o.G) for _ in range(32)]
+    cases = []
+    planned = 900
+    for i in range(planned):
+        p1 = pts[rng.randrange(32)]
+        p2 = other_point(pts, p1, rng)
+        pick = 0 if i % 4 == 0 else None
+        kind = i % 3
+        if kind == 0:
+            a = chud_rep(p1, rng.randrange(1, P), rng, pick=pick)
+            b = chud_rep(p2, rng.randrange(1, P), rng, pick=pick)
+            cases.append(("add_full", a + b))
+        elif kind == 1:
+            a = chud_rep(p1, rng.randrange(1, P), rng, yneg=rng.randrange(2) == 1, pick=pick)
+            cases.append((("madd_p", "madd_n")[rng.randrange(2)],
+                          a + [p2[0] * R % P, p2[1] * R % P, 0, 0]))
+        else:
+            y1 = p1[1] if rng.randrange(2) else P - p1[1]
+            cases.append((("aff_p", "aff_n")[rng.randrange(2)],
+                          [p1[0] * R % P, y1 * R % P, 0, 0, p2[0] * R % P, p2[1] * R % P, 0, 0]))
+    for i in range(12):   # degenerate full additions: false in both forms
+        p1 = pts[i]
+        cases.append(("add_full", chud_rep(p1, rng.randrange(1, P), rng) +
+                      chud_rep(p1, rng.randrange(1, P), rng, yneg=i % 2 == 1)))
+    assert len(cases) == planned + 12
+    seq = run_group(harness2, cases, wide=False)
+    wide = run_group(harness2, cases, wide=True)
+    bad = []
+    for k, ((op, _), s_row, w_rows) in enumerate(zip(cases, seq, wide)):
+        want_ret = 0 if k >= planned else 1
+        if int(s_row[36]) != want_ret or not (w_rows[:, 36] == want_ret).all():
+            bad.append((op, k, "ret"))
+        elif want_ret and not (w_rows == s_row[None, :]).all():
+            bad.append((op, k, np.nonzero((w_rows != s_row[None, :]).any(axis=1))[0][:4].tolist()))
+    assert not bad, (len(bad), bad[:10])
+
+
+def test_x_matches_r(harness2):
+    """The line that decides accept (x_matches_r, verify_finish's merged
+    product r ZZ + X (p - 1), then the same with r + N entering as un-carried
+    limbs) on pure field inputs X = x z^2 R, ZZ = z^2 R at their bounds, for
+    any x in [0, p): true exactly when r == x mod N -- r = x - N for x >= N,
+    up to x = p - 1, r = p - N - 1 -- and false for r +- 1, for r = x - N + 1,
+    for r = p - N with x = 0 and every r = x + p - N >= p - N (Go does not try
+    r + N there: a wrap mod p must not accept), and for r = x + N - p (a
+    verifier that subtracted N would accept).  r always in [1, N)."""
+    rng = random.Random(0xACCE)
+    xs = [0, 1, 2, N - 2, N - 1, N, N + 1, P - N - 2, P - N - 1, P - N, P - N + 1, P - 2, P - 1,
+          2 * N - P - 1, 2 * N - P, 2 * N - P + 1]
+    xs += [rng.randrange(N, P) for _ in range(150)]
+    xs += [rng.randrange(P - N) for _ in range(150)]
+    xs += [rng.randrange(P) for _ in range(300)]
+    xs += [rnd_value(rng, P) for _ in range(100)]
+    cases, meta = [], []
+
+    def add(x, r, name):
+        if not 1 <= r < N:
+            return
+        z = rng.randrange(1, P)
+        X = push_up(x * z * z * R % P, P, 1 << 258, rng)
+        ZZ = push_up(z * z * R % P, P, 1 << 258, rng)
+        cases.append(("x_matches", [X, ZZ, words(r)]))
+        meta.append((x, r, name))
+
+    for x in xs:
+        rt = x % N
+        add(x, rt, "true")
+        add(x, rt + 1, "r_plus_1")
+        add(x, rt - 1, "r_minus_1")
+        add(x, x - N + 1, "x_minus_N_plus_1")
+        add(x, x + P - N, "wraps_mod_p")        # r + N == x + p: only below 2N - p is r < N
+        add(x, x + N - P, "x_plus_N_minus_p")   # r == x + N (mod p)
+        add(x, rng.randrange(1, N), "random_r")
+    res = run(harness2, cases)
+    names = {m[2] for m in meta}
+    assert names == {"true", "r_plus_1", "r_minus_1", "x_minus_N_plus_1", "wraps_mod_p",
+                     "x_plus_N_minus_p", "random_r"}
+    assert (0, P - N, "wraps_mod_p") in meta and (P - 1, P - N - 1, "true") in meta
+    bad = []
+    for (x, r, name), (o0, _, _, _) in zip(meta, res):
+        want = x % N == r
+        assert want == (name == "true") or name == "random_r", (hex(x), hex(r), name)
+        if int(o0[0]) != int(want):
+            bad.append((name, hex(x), hex(r), int(o0[0])))
+    assert not bad, (len(bad), bad[:10])

@@ -44,7 +44,7 @@ def test_quirk_digest_constant():
     assert e.hex() == "52455155455354000000000000000140aff2e9d2d8922e47afd4648e69674971"
 
 
-PREHASHED = ["prehashed.json", "comb_windows.json"]
+PREHASHED = ["prehashed.json", "comb_windows.json", "scalar_edges.json"]
 
 
 @pytest.mark.parametrize("name", PREHASHED)
