@@ -19,12 +19,16 @@
 //     (../core/message-handling-batch.go) uses: the core keeps its
 //     per-message, per-stream order and its code, and hashes nothing.
 //
-// Generation never touches the GPU: GenerateMessageAuthenTag signs on the
-// CPU with the reference's own scheme (PublicAuthenScheme{crypto.SHA256,
+// Generation: GenerateMessageAuthenTag -- a lone call -- signs on the CPU
+// with the reference's own scheme (PublicAuthenScheme{crypto.SHA256,
 // EcdsaSigCipher}, crypto.go:63-76,113-116: Go's constant-time P-256), or
 // delegates to Config.Generator (the reference authenticator, which also
-// owns the SGX USIG).  The library's bulk signer (k_sign) is for synthetic
-// load only.
+// owns the SGX USIG).  With Config.GPUGenerate, BATCHES of tags for the
+// ECDSA roles are signed on the GPU (generate.go: GenerateBatch,
+// SignMessages) by the library's uniform-access signer, whose addresses,
+// branches and loop counts do not depend on the key or the nonce
+// (mbft_generate_tags_*, mbft_sign_messages_flat).  The library's older bulk
+// signer (k_sign, mbft_sign_prehashed*) stays for synthetic load only.
 //
 // Concurrency: any number of goroutines may call every method at once.
 // Batches are marshalled into a pool of arenas (one per in-flight batch), and
@@ -79,6 +83,11 @@ type Config struct {
 	// Private keys of the ECDSA roles this node signs as (CPU signing with
 	// the reference scheme, crypto.go:63-76), used when Generator is nil.
 	PrivateKeys map[api.AuthenticationRole]*ecdsa.PrivateKey
+	// GPUGenerate uploads the ReplicaAuthen / ClientAuthen PrivateKeys to the
+	// library and enables GenerateBatch and SignMessages (generate.go).
+	// Default false: no private key leaves Go memory, and
+	// GenerateMessageAuthenTag is the CPU path either way.
+	GPUGenerate bool
 	// Generator, if set, generates every tag: the reference authenticator
 	// built by authen.New / authen.NewWithSGXUSIG (USIG UIs stay in the SGX
 	// enclave).  USIGGenerator is the older name for the USIG role only.
@@ -121,6 +130,7 @@ type Authenticator struct {
 	gen     api.Authenticator
 	usigGen api.Authenticator
 	priv    map[api.AuthenticationRole]*ecdsa.PrivateKey
+	gpuGen  bool // Config.GPUGenerate: the ECDSA roles' private keys are in the library
 
 	arenas arenaPool   // batches are marshalled here (library page-locked memory)
 	keys   keyRegistry // the (role, id) pairs the context holds (keys.go)
@@ -199,6 +209,12 @@ func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnable
 		}
 	}
 	C.mbft_enable_usig(ctx, cBool(usigEnabled))
+	if cfg.GPUGenerate {
+		if err := a.uploadPrivateKeys(); err != nil {
+			a.Close()
+			return nil, err
+		}
+	}
 	conc := cfg.Concurrency
 	if conc == 0 {
 		conc = 4

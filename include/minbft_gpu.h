@@ -46,6 +46,16 @@
  *       constant-time P-256, crypto.go:63-76), as the Go binding does
  *       (go/gpuauth: GenerateMessageAuthenTag never calls the GPU).
  *
+ *   mbft_generate_tags_prehashed / _flat / _prehashed_device,
+ *   mbft_sign_messages_flat
+ *       NEW batch form of the same GenerateMessageAuthenTag for the ECDSA
+ *       roles, fit for real keys: a second signer (k_sign_tags) whose memory
+ *       addresses, branches and loop counts do not depend on the key or the
+ *       nonce, RFC 6979 nonces, DER on the device.  What the core signs per
+ *       executed request (REPLY: core/utils.go:43-53,
+ *       core/message-handling.go:552-568) and the client per request
+ *       (client/request.go:194-204).
+ *
  *   mbft_verify_prehashed / mbft_verify_prehashed_device
  *       Go crypto/ecdsa.Verify(pub, hash, r, s) as called at
  *       sample/authentication/crypto.go:86 and
@@ -633,6 +643,52 @@ int mbft_validate_replies(mbft_ctx* ctx, const mbft_message* msgs, size_t n, uin
  * verify launch), larger ones the GPU digest stage. */
 int mbft_validate_replies_flat(mbft_ctx* ctx, const mbft_msg_rec* recs, size_t n, const uint8_t* bytes,
                                size_t nbytes, uint32_t client_id, uint32_t flags, int32_t* out);
+
+/* Batch GenerateMessageAuthenTag for the ECDSA roles (new): n calls of
+ * api.Authenticator.GenerateMessageAuthenTag (api/api.go:133-144) -> the
+ * ecdsaSigCipher.Sign of sample/authentication/crypto.go:57-76 at once, with
+ * the role's private key from mbft_set_private_key, fit for real keys: the
+ * kernel's memory addresses, branches and loop counts do not depend on the
+ * key or the nonce.  The nonce is RFC 6979 (HMAC-SHA-256)
+ * where the reference draws from crypto/rand (crypto.go:65): tags are
+ * reproducible, verification does not depend on it.  Each tag is
+ * asn1.Marshal(ecdsaSignature{R, S}) (crypto.go:69) in a slot of
+ * MBFT_TAG_SLOT bytes (the rest of the slot zeroed), its length in
+ * tag_len[i]; an item that found no nonce in 4 candidates (unreachable in
+ * practice) gets length 0.  role: MBFT_ROLE_REPLICA or MBFT_ROLE_CLIENT; a
+ * role without a private key, or MBFT_ROLE_USIG, -> MBFT_ERR_STATE like the
+ * single call.  mbft_clear_keys also drops the private keys of these entry
+ * points (device copies zeroed, then freed): MBFT_ERR_STATE until
+ * mbft_set_private_key is called again.  Host buffers may be any memory.
+ *   mbft_generate_tags_prehashed  e: n x 32 bytes, the hashToInt input
+ *     (crypto.go:114,121 -> crypto/ecdsa.Sign).
+ *   mbft_generate_tags_flat  raw AuthenBytes msgs[msg_off[i], msg_off[i+1]):
+ *     e_i = (m_i || SHA256(""))[0:32] (crypto.go:114,121), built on the GPU.
+ *   mbft_generate_tags_prehashed_device  device buffers (d_e 4-byte aligned),
+ *     on the caller's stream, no synchronisation; the caller finishes that
+ *     stream's work before it changes keys.
+ *   mbft_sign_messages_flat  what the core and the client sign, from records
+ *     and arena as mbft_validate_messages_flat takes them: REPLY
+ *     (core/utils.go:43-53, core/message-handling.go:552-568) and
+ *     REQ-VIEW-CHANGE with the replica key, REQUEST (client/request.go:
+ *     194-204) with the client key; AuthenBytes (messages/authen.go:27-82,
+ *     SHA256 of op / result included) and e are built on the GPU in the same
+ *     kernel.  PREPARE / COMMIT (USIG UI: stays in SGX) or an unknown type,
+ *     or an op outside the arena -> MBFT_ERR_ARG, nothing written.
+ *   mbft_set_signer_window  the signer's generator table: 4, 5 (default) or
+ *     6 bits per window (33 / 52 / 87 KB, 64 / 52 / 43 additions); the table
+ *     is rebuilt on the next call, which first waits for the whole device
+ *     (a _device call on the caller's stream may still read the old one). */
+#define MBFT_TAG_SLOT 72
+int mbft_generate_tags_prehashed(mbft_ctx* ctx, uint32_t role, const uint8_t* e, size_t n,
+                                 uint8_t* tags, uint8_t* tag_len);
+int mbft_generate_tags_flat(mbft_ctx* ctx, uint32_t role, const uint8_t* msgs,
+                            const uint32_t* msg_off, size_t n, uint8_t* tags, uint8_t* tag_len);
+int mbft_generate_tags_prehashed_device(mbft_ctx* ctx, uint32_t role, const uint8_t* d_e, size_t n,
+                                        uint8_t* d_tags, uint8_t* d_tag_len, void* hip_stream);
+int mbft_sign_messages_flat(mbft_ctx* ctx, const mbft_msg_rec* recs, size_t n, const uint8_t* bytes,
+                            size_t nbytes, uint8_t* tags, uint8_t* tag_len);
+int mbft_set_signer_window(mbft_ctx* ctx, int wbits);
 
 /* Host-only helpers (no GPU). */
 /* encoding/asn1 DER decode of struct{R, S *big.Int}.

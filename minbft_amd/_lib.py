@@ -42,6 +42,9 @@ ROLE_REPLICA = 1
 ROLE_USIG = 2
 ROLE_CLIENT = 3
 
+#: bytes per tag slot of the batch signer (MBFT_TAG_SLOT)
+TAG_SLOT = 72
+
 #: every symbol include/minbft_gpu.h declares (checked by tests/test_abi.py)
 EXPORTED = [
     "mbft_version", "mbft_device_count", "mbft_ctx_create", "mbft_ctx_destroy",
@@ -66,6 +69,8 @@ EXPORTED = [
     "mbft_check_coalescing_stats", "mbft_set_small_check", "mbft_debug_sha256",
     "mbft_validate_replies_flat", "mbft_set_resident", "mbft_resident_stats", "mbft_resident_wait_stats", "mbft_debug_threads_started",
     "mbft_debug_host_join", "mbft_debug_host_scalars",
+    "mbft_generate_tags_prehashed", "mbft_generate_tags_flat", "mbft_generate_tags_prehashed_device",
+    "mbft_sign_messages_flat", "mbft_set_signer_window",
 ]
 
 # enum mbft_msg_type / mbft_stage / mbft_validate_flags
@@ -265,6 +270,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_sign_prehashed": (i, [vp, u8p, sz, vp, u8p, sz, vp, vp]),
         "mbft_sign_prehashed_device": (i, [vp, vp, vp, vp, sz, vp, vp, vp]),
         "mbft_sign_nonce_device": (i, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "mbft_generate_tags_prehashed": (i, [vp, u32, vp, sz, vp, vp]),
+        "mbft_generate_tags_flat": (i, [vp, u32, vp, vp, sz, vp, vp]),
+        "mbft_generate_tags_prehashed_device": (i, [vp, u32, vp, sz, vp, vp, vp]),
+        "mbft_sign_messages_flat": (i, [vp, vp, sz, vp, sz, vp, vp]),
+        "mbft_set_signer_window": (i, [vp, i]),
         "mbft_der_parse_sig": (i, [u8p, sz, vp, vp, ctypes.POINTER(sz)]),
         "mbft_sha256": (None, [u8p, sz, vp]),
         "mbft_profile_enable": (i, [vp, i]),

@@ -567,6 +567,63 @@ class Authenticator:
                                                  _buf(e), n, _buf(r), _buf(s)), "sign_prehashed")
         return r, s
 
+    # ------------------------------------------------- batch generation
+    # n GenerateMessageAuthenTag calls of an ECDSA role at once, with the
+    # role's private key (set_private_key), by the uniform-access signer
+    # (include/minbft_gpu.h).  Host forms return (tags, lens):
+    # tags n x 72 uint8 (one slot per tag, the rest of a slot zeroed), lens n
+    # uint8 (0: the item found no nonce -- unreachable in practice).
+    def set_signer_window(self, wbits: int):
+        """The signer's generator table: 4, 5 (default) or 6 bits per window."""
+        self._check(self.lib.mbft_set_signer_window(self.ctx, wbits), "set_signer_window")
+
+    def generate_tags_prehashed(self, role: int, e: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """mbft_generate_tags_prehashed: e n x 32 bytes, the hashToInt inputs."""
+        e = np.ascontiguousarray(e, dtype=np.uint8).reshape(-1, 32)
+        n = e.shape[0]
+        tags = np.zeros((n, _lib.TAG_SLOT), dtype=np.uint8)
+        lens = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.mbft_generate_tags_prehashed(self.ctx, role, _buf(e), n, _buf(tags),
+                                                          _buf(lens)), "generate_tags_prehashed")
+        return tags, lens
+
+    def generate_tags(self, role: int, msgs) -> Tuple[np.ndarray, np.ndarray]:
+        """mbft_generate_tags_flat over a list of raw AuthenBytes: tag i is
+        GenerateMessageAuthenTag(role, msgs[i])."""
+        n = len(msgs)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+        data = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\0", dtype=np.uint8)
+        tags = np.zeros((n, _lib.TAG_SLOT), dtype=np.uint8)
+        lens = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.mbft_generate_tags_flat(self.ctx, role, _buf(data), _buf(off), n, _buf(tags),
+                                                     _buf(lens)), "generate_tags")
+        return tags, lens
+
+    def generate_tags_prehashed_device(self, role: int, d_e: int, n: int, d_tags: int, d_lens: int,
+                                       stream: int = 0) -> None:
+        """mbft_generate_tags_prehashed_device: device pointers (e n x 32,
+        tags n x 72, lens n), on `stream`, not synchronised."""
+        self._check(self.lib.mbft_generate_tags_prehashed_device(
+            self.ctx, role, ctypes.c_void_p(d_e), n, ctypes.c_void_p(d_tags), ctypes.c_void_p(d_lens),
+            ctypes.c_void_p(stream)), "generate_tags_prehashed_device")
+
+    def sign_messages_flat(self, recs: np.ndarray, arena: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """mbft_sign_messages_flat over records + arena (pack_messages): REPLY
+        and REQ-VIEW-CHANGE with the replica key, REQUEST with the client key."""
+        n = recs.shape[0]
+        tags = np.zeros((n, _lib.TAG_SLOT), dtype=np.uint8)
+        lens = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.mbft_sign_messages_flat(self.ctx, _buf(recs), n, _buf(arena), arena.nbytes,
+                                                     _buf(tags), _buf(lens)), "sign_messages_flat")
+        return tags, lens
+
+    @staticmethod
+    def tag_bytes(tags: np.ndarray, lens: np.ndarray) -> list:
+        """(tags, lens) of the batch generators -> the tags as `bytes`."""
+        tags = np.asarray(tags, dtype=np.uint8).reshape(-1, _lib.TAG_SLOT)
+        return [bytes(tags[i, : int(lens[i])]) for i in range(tags.shape[0])]
+
     # ---------------------------------------------------------- profiling
     def profile(self, enable: bool = True):
         """Record HIP events around the inversion and verify kernels of every

@@ -733,6 +733,7 @@ void mbft_ctx_destroy(mbft_ctx* c) {
   c->peers.clear();
   hipSetDevice(c->device);
   c->pool.reset();
+  sign_destroy(c);
   for (hipStream_t st : {c->stream, c->istream, c->cstream, c->cstream2, c->vstream[0], c->vstream[1], c->kstream})
     if (st) hipStreamSynchronize(st);
   for (auto& ev : c->evs) {
@@ -992,6 +993,9 @@ int mbft_clear_keys(mbft_ctx* c) {
   c->fp_group_of.clear();
   c->epoch_val.clear();
   c->epoch_set.clear();
+  // the batch signer's device keys go too (zeroed, then freed): batch
+  // generation needs mbft_set_private_key again
+  sign_keys_wipe(c);
   return MBFT_OK;
 }
 
@@ -1007,6 +1011,10 @@ int mbft_key_slot(const mbft_ctx* c, uint32_t role, uint32_t id) {
 int mbft_set_private_key(mbft_ctx* c, uint32_t role, const uint8_t d[32]) {
   if (!c || !d) return MBFT_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
+  // the batch signer's copy on the device first (sign.cpp): if that fails
+  // the call fails as a whole and the single call's key stays what it was
+  if (hipSetDevice(c->device) != hipSuccess) return MBFT_ERR_HIP;
+  if (const int rc = sign_key_set(c, role, d)) return rc;
   std::array<uint8_t, 32> k;
   memcpy(k.data(), d, 32);
   c->priv[role] = k;

@@ -22,6 +22,7 @@
 
 #include "../../include/minbft_gpu.h"
 #include "kernels.h"
+#include "sign_kernels.h"
 #include "sha256.h"
 
 namespace mbft_host {
@@ -408,6 +409,15 @@ struct mbft_ctx {
   std::vector<uint64_t> epoch_val;
   std::vector<uint8_t> epoch_set;
   std::map<uint32_t, std::array<uint8_t, 32>> priv;
+  // The batch signer (sign.cpp, mbft_generate_tags_* / mbft_sign_messages_flat):
+  // the ECDSA roles' private keys on the device, 32 bytes each ([0] replica,
+  // [1] client; uploaded by mbft_set_private_key, zeroed before they are
+  // freed), its own small generator table (window sign_w, built on first use)
+  // and its staging.
+  void* sign_key[2] = {nullptr, nullptr};
+  uint32_t* sign_tab = nullptr;
+  int sign_w = mbft_launch::kSignDefaultWindow, sign_tab_w = 0;
+  mbft_host::DevBuf sg_in, sg_off, sg_recs, sg_tags, sg_len;
 
   // scratch
   mbft_host::DevBuf e, r, s, slot, status, xy, ok, bpts, priv_d;
@@ -642,6 +652,15 @@ struct Lease {
 
 int fail(mbft_ctx* c, int code, const std::string& what);
 int hip_fail(mbft_ctx* c, hipError_t e, const char* what);
+
+// The batch signer's device key buffers (sign.cpp).  sign_key_set: role's
+// key goes to its 32-byte device buffer (an earlier key is zeroed first; roles
+// other than replica / client have none: MBFT_OK).  sign_keys_wipe: every
+// buffer zeroed, then freed.  sign_destroy: that and the signer's table and
+// staging.  All under the context lock, device set.
+int sign_key_set(mbft_ctx* c, uint32_t role, const uint8_t d[32]);
+void sign_keys_wipe(mbft_ctx* c);
+void sign_destroy(mbft_ctx* c);
 
 #define HIPCHK(c, x)                                                    \
   do {                                                                  \
