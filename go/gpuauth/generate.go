@@ -14,7 +14,8 @@ package gpuauth
 // identically.
 //
 // GenerateMessageAuthenTag itself stays on the CPU (gpuauth.go): a lone call
-// is served by Go's signer; USIG UIs stay in the SGX enclave.
+// is served by Go's signer; USIG UIs stay in the SGX enclave unless
+// Config.GPUUSIG starts the software USIG (usig.go).
 
 /*
 #include "minbft_gpu.h"

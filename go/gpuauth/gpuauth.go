@@ -29,6 +29,10 @@
 // branches and loop counts do not depend on the key or the nonce
 // (mbft_generate_tags_*, mbft_sign_messages_flat).  The library's older bulk
 // signer (k_sign, mbft_sign_prehashed*) stays for synthetic load only.
+// With Config.GPUUSIG (default off) the USIG role's UIs come from the
+// library's SOFTWARE USIG (usig.go) instead of the enclave: for hosts without
+// SGX, with none of the trusted-hardware guarantee -- the equivalent of the
+// SGX SDK's simulation mode.
 //
 // Concurrency: any number of goroutines may call every method at once.
 // Batches are marshalled into a pool of arenas (one per in-flight batch), and
@@ -68,6 +72,7 @@ import (
 
 	"github.com/hyperledger-labs/minbft/api"
 	authen "github.com/hyperledger-labs/minbft/sample/authentication"
+	"github.com/hyperledger-labs/minbft/usig"
 )
 
 // Config selects the devices and the comb-table windows (include/minbft_gpu.h:
@@ -88,6 +93,13 @@ type Config struct {
 	// Default false: no private key leaves Go memory, and
 	// GenerateMessageAuthenTag is the CPU path either way.
 	GPUGenerate bool
+	// GPUUSIG starts a SOFTWARE USIG in the library from
+	// PrivateKeys[api.USIGAuthen] with a random epoch (usig.go: USIG,
+	// CreateUIs) and routes GenerateMessageAuthenTag in the USIG role through
+	// it.  It has none of the trusted-hardware guarantee MinBFT's f < n/2
+	// bound rests on -- the equivalent of the SGX SDK's simulation mode, for
+	// hosts without SGX.  Default false.
+	GPUUSIG bool
 	// Generator, if set, generates every tag: the reference authenticator
 	// built by authen.New / authen.NewWithSGXUSIG (USIG UIs stay in the SGX
 	// enclave).  USIGGenerator is the older name for the USIG role only.
@@ -131,6 +143,10 @@ type Authenticator struct {
 	usigGen api.Authenticator
 	priv    map[api.AuthenticationRole]*ecdsa.PrivateKey
 	gpuGen  bool // Config.GPUGenerate: the ECDSA roles' private keys are in the library
+	usig    *USIG // Config.GPUUSIG: the software USIG (usig.go), else nil
+
+	// the USIGAuthen public keys New was given (USIG.VerifyUI finds a USIG ID's replica here)
+	usigKeys map[uint32]*ecdsa.PublicKey
 
 	arenas arenaPool   // batches are marshalled here (library page-locked memory)
 	keys   keyRegistry // the (role, id) pairs the context holds (keys.go)
@@ -159,7 +175,7 @@ func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnable
 		return nil, fmt.Errorf("mbft_ctx_create(%d): %d", devices[0], int(rc))
 	}
 	a := &Authenticator{ctx: ctx, gen: cfg.Generator, usigGen: cfg.USIGGenerator,
-		priv: cfg.PrivateKeys}
+		priv: cfg.PrivateKeys, usigKeys: keys[api.USIGAuthen]}
 	a.arenas.init(16)
 	fail := func(what string, rc C.int) (*Authenticator, error) {
 		err := fmt.Errorf("%s: %d (%s)", what, int(rc), C.GoString(C.mbft_last_error(ctx)))
@@ -211,6 +227,12 @@ func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnable
 	C.mbft_enable_usig(ctx, cBool(usigEnabled))
 	if cfg.GPUGenerate {
 		if err := a.uploadPrivateKeys(); err != nil {
+			a.Close()
+			return nil, err
+		}
+	}
+	if cfg.GPUUSIG {
+		if err := a.startUSIG(); err != nil {
 			a.Close()
 			return nil, err
 		}
@@ -403,9 +425,17 @@ func (a *Authenticator) VerifyBatch(calls []Call) []error {
 // reference authenticator (Config.Generator) if given, else the
 // reference's ECDSA scheme with Config.PrivateKeys (Sum(m) digest, DER,
 // crypto.go:63-76,113-116); the USIG role needs the SGX-backed reference
-// authenticator.
+// authenticator -- or, with Config.GPUUSIG, takes the next UI of the
+// library's software USIG (usig.go; no trusted hardware behind it).
 func (a *Authenticator) GenerateMessageAuthenTag(role api.AuthenticationRole,
 	msg []byte) ([]byte, error) {
+	if role == api.USIGAuthen && a.usig != nil {
+		ui, err := a.usig.CreateUI(msg)
+		if err != nil {
+			return nil, err
+		}
+		return usig.MustMarshalUI(ui), nil
+	}
 	if a.gen != nil {
 		return a.gen.GenerateMessageAuthenTag(role, msg)
 	}

@@ -39,7 +39,10 @@
  *       api/api.go:143 GenerateMessageAuthenTag for the ECDSA roles
  *       (crypto.go:63-76,113-116: sign SHA256("")-suffixed digest, DER).
  *       The nonce is deterministic (RFC 6979-style) instead of crypto/rand;
- *       tags verify identically.  USIG generation stays in the SGX enclave.
+ *       tags verify identically.  In the USIG role it creates one UI from the
+ *       context's software USIG (mbft_usig_init, below) and is
+ *       MBFT_ERR_STATE without one; tag_cap must then be at least
+ *       MBFT_UI_SLOT.  The ECDSA roles' single call is
  *       NOT CONSTANT-TIME (the GPU signer, k_sign, gathers comb entries at
  *       addresses set by the nonce's digits): for tests and synthetic load
  *       only.  A production signer keeps the reference's CPU path (Go's
@@ -656,8 +659,8 @@ int mbft_validate_replies_flat(mbft_ctx* ctx, const mbft_msg_rec* recs, size_t n
  * MBFT_TAG_SLOT bytes (the rest of the slot zeroed), its length in
  * tag_len[i]; an item that found no nonce in 4 candidates (unreachable in
  * practice) gets length 0.  role: MBFT_ROLE_REPLICA or MBFT_ROLE_CLIENT; a
- * role without a private key, or MBFT_ROLE_USIG, -> MBFT_ERR_STATE like the
- * single call.  mbft_clear_keys also drops the private keys of these entry
+ * role without a private key, or MBFT_ROLE_USIG (UIs come from
+ * mbft_usig_create_uis_*), -> MBFT_ERR_STATE.  mbft_clear_keys also drops the private keys of these entry
  * points (device copies zeroed, then freed): MBFT_ERR_STATE until
  * mbft_set_private_key is called again.  Host buffers may be any memory.
  *   mbft_generate_tags_prehashed  e: n x 32 bytes, the hashToInt input
@@ -673,8 +676,9 @@ int mbft_validate_replies_flat(mbft_ctx* ctx, const mbft_msg_rec* recs, size_t n
  *     REQ-VIEW-CHANGE with the replica key, REQUEST (client/request.go:
  *     194-204) with the client key; AuthenBytes (messages/authen.go:27-82,
  *     SHA256 of op / result included) and e are built on the GPU in the same
- *     kernel.  PREPARE / COMMIT (USIG UI: stays in SGX) or an unknown type,
- *     or an op outside the arena -> MBFT_ERR_ARG, nothing written.
+ *     kernel.  PREPARE / COMMIT (they carry a USIG UI, not an ECDSA-role tag:
+ *     mbft_usig_sign_messages_flat below) or an unknown type, or an op outside
+ *     the arena -> MBFT_ERR_ARG, nothing written.
  *   mbft_set_signer_window  the signer's generator table: 4, 5 (default) or
  *     6 bits per window (33 / 52 / 87 KB, 64 / 52 / 43 additions); the table
  *     is rebuilt on the next call, which first waits for the whole device
@@ -689,6 +693,76 @@ int mbft_generate_tags_prehashed_device(mbft_ctx* ctx, uint32_t role, const uint
 int mbft_sign_messages_flat(mbft_ctx* ctx, const mbft_msg_rec* recs, size_t n, const uint8_t* bytes,
                             size_t nbytes, uint8_t* tags, uint8_t* tag_len);
 int mbft_set_signer_window(mbft_ctx* ctx, int wbits);
+
+/* A software USIG (new): CreateUI for PREPARE and COMMIT on hosts without SGX
+ * (an MI355X host is an EPYC machine).  Replaces the enclave's
+ * ecall_usig_create_ui (usig/sgx/enclave/usig.c:36-76) with its Go wrapper
+ * (usig/sgx/sgx-usig.go:52-64 CreateUI, :71-79 ID), batch by batch, through
+ * the uniform-access signer of the entry points above (k_usig_uis; RFC 6979
+ * nonce, so a UI is reproducible from (d, epoch, counter, message)).
+ *
+ * NO TRUSTED HARDWARE.  MinBFT tolerates f < n/2 faults only because a faulty
+ * replica cannot make its USIG sign two messages under one counter.  Here the
+ * counter and the key are ordinary process state: whoever controls the host
+ * controls them.  This is the equivalent of the SGX SDK's simulation mode --
+ * for development, tests and benchmarks on this machine class -- and the Go
+ * binding keeps it off unless asked (Config.GPUUSIG).
+ *
+ * Semantics kept from the enclave: the epoch is fixed per instance; the
+ * counter starts at 1 and moves only when valid signatures are handed out;
+ * the signed digest is SHA256(SHA256(m) || epoch_le64 || counter_le64)
+ * (sgx-usig.go:99-101, usig-enclave.go:204-214); a UI is counter_be64 ||
+ * epoch_be64 || asn1.Marshal{R, S} (usig/usig.go:54-86, sgx-usig.go:143-168),
+ * at most MBFT_UI_SLOT bytes: each UI sits in a slot of that size, the rest
+ * of the slot zeroed, its length in ui_len[i].
+ *
+ * The counter contract: calls on one context are serialised; a call takes the
+ * counters [next, next + n) for items 0 .. n-1, runs the kernel, copies the
+ * UIs out and only then advances next by n, reporting the first counter in
+ * *first_counter.  If anything fails (launch, copy, an item without a usable
+ * nonce) the call returns an error, zeroes uis and ui_len, and leaves the
+ * counter where it was: no counter value appears in two UIs that left the
+ * library, and successful calls leave no gaps (peerstate's CaptureUI waits
+ * forever on a gap).  There is no device-pointer / caller-stream form: without
+ * a synchronisation the library could not know that a UI was exposed.  The
+ * counter is not persisted: a restart is a new instance with a new epoch, as
+ * for the enclave.  On a multi-device context the instance lives on the
+ * context's first device.
+ *   mbft_usig_init  a new instance: key d (32 B big-endian, into a device
+ *     buffer that is zeroed before it is freed), the epoch (the enclave draws
+ *     it from sgx_read_rand, usig.c:177-184: pass random bits), counter 1.
+ *     d = 0 or d >= N -> MBFT_ERR_KEY; an epoch equal to that of this
+ *     context's previous instance -> MBFT_ERR_STATE (either leaves an existing
+ *     instance as it is).  Replaces an existing instance.  Independent of
+ *     mbft_set_private_key(MBFT_ROLE_USIG, ...), which it neither reads nor
+ *     changes.  mbft_clear_keys and mbft_ctx_destroy drop the instance (key
+ *     zeroed, then freed): every entry point here is MBFT_ERR_STATE until the
+ *     next mbft_usig_init, which needs a fresh epoch.
+ *   mbft_usig_id  the identity epoch_be64 || PKIX(d G) (sgx-usig.go:105-139),
+ *     MBFT_USIG_ID_LEN bytes; *len receives that size, MBFT_ERR_ARG when cap
+ *     is smaller.  d G comes from the same uniform comb as a nonce's point.
+ *   mbft_usig_next_counter  the counter the next UI will carry.
+ *   mbft_usig_create_uis_digests  UI i over the message whose SHA256 is
+ *     digests[32 i .. 32 i + 32).
+ *   mbft_usig_create_uis_flat  UI i over the raw message
+ *     msgs[msg_off[i], msg_off[i+1]), hashed on the GPU.
+ *   mbft_usig_sign_messages_flat  UI i over AuthenBytes(recs[i])
+ *     (messages/authen.go:27-82) for PREPARE (core/prepare.go) and COMMIT
+ *     (core/commit.go: prep_replica_id and prep_ui_counter name the PREPARE)
+ *     records over an arena, as mbft_validate_messages_flat takes them, built
+ *     and hashed on the GPU.  Any other type, or an op outside the arena ->
+ *     MBFT_ERR_ARG, nothing written, the counter untouched. */
+#define MBFT_UI_SLOT 88
+#define MBFT_USIG_ID_LEN 99
+int mbft_usig_init(mbft_ctx* ctx, const uint8_t d[32], uint64_t epoch);
+int mbft_usig_id(mbft_ctx* ctx, uint8_t* out, size_t cap, size_t* len);
+int mbft_usig_next_counter(mbft_ctx* ctx, uint64_t* counter);
+int mbft_usig_create_uis_digests(mbft_ctx* ctx, const uint8_t* digests, size_t n, uint8_t* uis,
+                                 uint8_t* ui_len, uint64_t* first_counter);
+int mbft_usig_create_uis_flat(mbft_ctx* ctx, const uint8_t* msgs, const uint32_t* msg_off, size_t n,
+                              uint8_t* uis, uint8_t* ui_len, uint64_t* first_counter);
+int mbft_usig_sign_messages_flat(mbft_ctx* ctx, const mbft_msg_rec* recs, size_t n, const uint8_t* bytes,
+                                 size_t nbytes, uint8_t* uis, uint8_t* ui_len, uint64_t* first_counter);
 
 /* Host-only helpers (no GPU). */
 /* encoding/asn1 DER decode of struct{R, S *big.Int}.

@@ -44,6 +44,9 @@ ROLE_CLIENT = 3
 
 #: bytes per tag slot of the batch signer (MBFT_TAG_SLOT)
 TAG_SLOT = 72
+#: bytes per UI slot of the software USIG (MBFT_UI_SLOT) and of its identity
+UI_SLOT = 88
+USIG_ID_LEN = 99
 
 #: every symbol include/minbft_gpu.h declares (checked by tests/test_abi.py)
 EXPORTED = [
@@ -71,6 +74,8 @@ EXPORTED = [
     "mbft_debug_host_join", "mbft_debug_host_scalars",
     "mbft_generate_tags_prehashed", "mbft_generate_tags_flat", "mbft_generate_tags_prehashed_device",
     "mbft_sign_messages_flat", "mbft_set_signer_window",
+    "mbft_usig_init", "mbft_usig_id", "mbft_usig_next_counter", "mbft_usig_create_uis_digests",
+    "mbft_usig_create_uis_flat", "mbft_usig_sign_messages_flat",
 ]
 
 # enum mbft_msg_type / mbft_stage / mbft_validate_flags
@@ -275,6 +280,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_generate_tags_prehashed_device": (i, [vp, u32, vp, sz, vp, vp, vp]),
         "mbft_sign_messages_flat": (i, [vp, vp, sz, vp, sz, vp, vp]),
         "mbft_set_signer_window": (i, [vp, i]),
+        "mbft_usig_init": (i, [vp, u8p, ctypes.c_uint64]),
+        "mbft_usig_id": (i, [vp, vp, sz, ctypes.POINTER(sz)]),
+        "mbft_usig_next_counter": (i, [vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "mbft_usig_create_uis_digests": (i, [vp, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "mbft_usig_create_uis_flat": (i, [vp, vp, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "mbft_usig_sign_messages_flat": (i, [vp, vp, sz, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_uint64)]),
         "mbft_der_parse_sig": (i, [u8p, sz, vp, vp, ctypes.POINTER(sz)]),
         "mbft_sha256": (None, [u8p, sz, vp]),
         "mbft_profile_enable": (i, [vp, i]),

@@ -17,6 +17,7 @@ Every call goes through ``libminbft_amd.so``; there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes
+import os
 import sys as _sys
 from typing import Iterable, Optional, Sequence, Tuple
 
@@ -293,9 +294,9 @@ class Authenticator:
         raise AuthenticationError(st)
 
     def GenerateMessageAuthenTag(self, role: int, msg: bytes) -> bytes:
-        out = ctypes.create_string_buffer(80)
+        out = ctypes.create_string_buffer(96)  # an ECDSA tag (72) or a USIG UI (88)
         n = ctypes.c_size_t(0)
-        self._check(self.lib.mbft_generate_message_authen_tag(self.ctx, role, msg, len(msg), out, 80,
+        self._check(self.lib.mbft_generate_message_authen_tag(self.ctx, role, msg, len(msg), out, 96,
                                                               ctypes.byref(n)), "generate")
         return out.raw[:n.value]
 
@@ -623,6 +624,77 @@ class Authenticator:
         """(tags, lens) of the batch generators -> the tags as `bytes`."""
         tags = np.asarray(tags, dtype=np.uint8).reshape(-1, _lib.TAG_SLOT)
         return [bytes(tags[i, : int(lens[i])]) for i in range(tags.shape[0])]
+
+    # ------------------------------------------------------ software USIG
+    # CreateUI for PREPARE / COMMIT without SGX (include/minbft_gpu.h,
+    # DESIGN.md §4.6).  NO trusted hardware behind it: the equivalent of the
+    # SGX SDK's simulation mode.  The create_* forms return (uis, lens, first):
+    # uis n x 88 uint8 (one slot per UI, the rest of a slot zeroed), lens n
+    # uint8, first = the counter of UI 0 (UI i carries first + i).
+    def usig_init(self, d: bytes, epoch: Optional[int] = None) -> int:
+        """A new USIG instance with key d (32 bytes big-endian) and counter 1;
+        the epoch is drawn from os.urandom unless given.  Returns the epoch."""
+        if len(d) != 32:
+            raise ValueError("USIG key must be 32 bytes")
+        if epoch is None:
+            epoch = int.from_bytes(os.urandom(8), "big")
+        self._check(self.lib.mbft_usig_init(self.ctx, d, epoch), "usig_init")
+        return epoch
+
+    def usig_id(self) -> bytes:
+        """epoch_be64 || PKIX(public key) (sgx-usig.go MakeID)."""
+        out = ctypes.create_string_buffer(_lib.USIG_ID_LEN)
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.mbft_usig_id(self.ctx, out, _lib.USIG_ID_LEN, ctypes.byref(n)), "usig_id")
+        return out.raw[:n.value]
+
+    def usig_next_counter(self) -> int:
+        c = ctypes.c_uint64(0)
+        self._check(self.lib.mbft_usig_next_counter(self.ctx, ctypes.byref(c)), "usig_next_counter")
+        return c.value
+
+    def usig_create_uis_digests(self, digests: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
+        """mbft_usig_create_uis_digests: digests n x 32 bytes, SHA256 of each message."""
+        dg = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        n = dg.shape[0]
+        uis = np.zeros((n, _lib.UI_SLOT), dtype=np.uint8)
+        lens = np.zeros(n, dtype=np.uint8)
+        first = ctypes.c_uint64(0)
+        self._check(self.lib.mbft_usig_create_uis_digests(self.ctx, _buf(dg), n, _buf(uis), _buf(lens),
+                                                          ctypes.byref(first)), "usig_create_uis_digests")
+        return uis, lens, first.value
+
+    def usig_create_uis(self, msgs) -> Tuple[np.ndarray, np.ndarray, int]:
+        """mbft_usig_create_uis_flat over a list of raw messages: UI i is
+        CreateUI(msgs[i])."""
+        n = len(msgs)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+        data = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\0", dtype=np.uint8)
+        uis = np.zeros((n, _lib.UI_SLOT), dtype=np.uint8)
+        lens = np.zeros(n, dtype=np.uint8)
+        first = ctypes.c_uint64(0)
+        self._check(self.lib.mbft_usig_create_uis_flat(self.ctx, _buf(data), _buf(off), n, _buf(uis), _buf(lens),
+                                                       ctypes.byref(first)), "usig_create_uis")
+        return uis, lens, first.value
+
+    def usig_sign_messages_flat(self, recs: np.ndarray, arena: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
+        """mbft_usig_sign_messages_flat over PREPARE / COMMIT records + arena
+        (pack_messages): UI i is CreateUI(AuthenBytes(recs[i]))."""
+        n = recs.shape[0]
+        uis = np.zeros((n, _lib.UI_SLOT), dtype=np.uint8)
+        lens = np.zeros(n, dtype=np.uint8)
+        first = ctypes.c_uint64(0)
+        self._check(self.lib.mbft_usig_sign_messages_flat(self.ctx, _buf(recs), n, _buf(arena), arena.nbytes,
+                                                          _buf(uis), _buf(lens), ctypes.byref(first)),
+                    "usig_sign_messages_flat")
+        return uis, lens, first.value
+
+    @staticmethod
+    def ui_bytes(uis: np.ndarray, lens: np.ndarray) -> list:
+        """(uis, lens) of the USIG batch forms -> the marshalled UIs as `bytes`."""
+        uis = np.asarray(uis, dtype=np.uint8).reshape(-1, _lib.UI_SLOT)
+        return [bytes(uis[i, : int(lens[i])]) for i in range(uis.shape[0])]
 
     # ---------------------------------------------------------- profiling
     def profile(self, enable: bool = True):

@@ -22,6 +22,9 @@ LIB = os.path.join(HERE, "libminbft_amd.so")
 OBJDIR = os.path.join(HERE, "build")
 
 ARCH = os.environ.get("MBFT_OFFLOAD_ARCH", "gfx950")
+# every translation unit's flags (tests/test_sign_resources.py compiles the
+# signer's kernels with the same ones)
+COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I", os.path.join(ROOT, "include")]
 
 DEVICE_SOURCES = ["kernels.hip", "msg_kernels.hip", "sign_kernels.hip"]
 HOST_SOURCES = ["host.cpp", "der.cpp", "messages.cpp", "batch.cpp", "msgdev.cpp", "winv_host.cpp",
@@ -74,7 +77,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return LIB
     hipcc = _hipcc()
     os.makedirs(OBJDIR, exist_ok=True)
-    common = ["-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I", os.path.join(ROOT, "include")]
+    common = COMMON_FLAGS
     jobs = []
     for f in DEVICE_SOURCES:
         obj = os.path.join(OBJDIR, f + ".o")

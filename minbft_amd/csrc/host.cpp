@@ -1141,12 +1141,14 @@ int mbft_generate_message_authen_tag(mbft_ctx* c, uint32_t role, const uint8_t* 
                                      size_t msg_len, uint8_t* tag_out, size_t tag_cap,
                                      size_t* tag_len) {
   if (!c || (msg_len && !msg) || !tag_out || !tag_len) return MBFT_ERR_ARG;
+  // the USIG role: one UI from the context's software USIG (sign.cpp), if
+  // mbft_usig_init made one; a key from mbft_set_private_key never signs here
+  if (role == MBFT_ROLE_USIG) return usig_single(c, msg, msg_len, tag_out, tag_cap, tag_len);
   std::array<uint8_t, 32> d;
   {
     std::lock_guard<std::mutex> g(c->mu);
     auto it = c->priv.find(role);
-    if (it == c->priv.end() || role == MBFT_ROLE_USIG)
-      return fail(c, MBFT_ERR_STATE, "no ECDSA private key for role");
+    if (it == c->priv.end()) return fail(c, MBFT_ERR_STATE, "no ECDSA private key for role");
     d = it->second;
   }
   uint8_t e32[32], r[32], s[32];

@@ -418,6 +418,16 @@ struct mbft_ctx {
   uint32_t* sign_tab = nullptr;
   int sign_w = mbft_launch::kSignDefaultWindow, sign_tab_w = 0;
   mbft_host::DevBuf sg_in, sg_off, sg_recs, sg_tags, sg_len;
+  // The software USIG instance (sign.cpp, mbft_usig_*), all
+  // under mu: its key on the device (32 bytes, zeroed before it is freed),
+  // the epoch, the next counter to hand out (from 1), the identity
+  // epoch_be64 || PKIX(d G), and the epoch of this context's last instance
+  // (a new one must differ).  usig_key == null: no instance.
+  void* usig_key = nullptr;
+  uint64_t usig_epoch = 0, usig_next = 0;
+  uint64_t usig_last_epoch = 0;
+  bool usig_had = false;
+  uint8_t usig_ident[8 + 91] = {};
 
   // scratch
   mbft_host::DevBuf e, r, s, slot, status, xy, ok, bpts, priv_d;
@@ -661,6 +671,11 @@ int hip_fail(mbft_ctx* c, hipError_t e, const char* what);
 int sign_key_set(mbft_ctx* c, uint32_t role, const uint8_t d[32]);
 void sign_keys_wipe(mbft_ctx* c);
 void sign_destroy(mbft_ctx* c);
+// mbft_generate_message_authen_tag in the USIG role (sign.cpp): one UI over
+// msg from the context's software USIG, MBFT_ERR_STATE without an instance.
+// Takes the context lock itself.
+int usig_single(mbft_ctx* c, const uint8_t* msg, size_t msg_len, uint8_t* tag_out, size_t tag_cap,
+                size_t* tag_len);
 
 #define HIPCHK(c, x)                                                    \
   do {                                                                  \

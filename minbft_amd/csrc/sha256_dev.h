@@ -44,8 +44,9 @@ __device__ __forceinline__ void sha256_msg(uint32_t h[8], const uint8_t* p, uint
 }
 
 // SHA256(d32 || epoch_le64 || counter_le64) for a 32-byte digest given as
-// big-endian-numeric words (usig/sgx/usig-enclave.go:204-214).
-__device__ __forceinline__ void sha256_usig_chain(uint32_t out[8], const uint32_t d[8],
+// big-endian-numeric words (usig/sgx/usig-enclave.go:204-214).  Host and
+// device: tests/csrc/usig_check.cpp runs it on the CPU.
+MBFT_HD void sha256_usig_chain(uint32_t out[8], const uint32_t d[8],
                                                   uint64_t epoch, uint64_t counter) {
   uint32_t m[16];
 #pragma unroll

@@ -6,7 +6,9 @@
 //  * the signed window recoding of the nonce (sign_digit) -- the digits of
 //    the comb layout in kernels.hip (k_table_fill) -- and
 //  * the masked pick of a lane's table entry out of a whole window read at
-//    wave-uniform addresses (sign_pick).
+//    wave-uniform addresses (sign_pick);
+//  * the byte format of a software-USIG UI (usig_ui_write; k_usig_uis,
+//    tests/csrc/usig_check.cpp).
 // Nothing here indexes memory, branches or bounds a loop by a secret; the one
 // exception is rfc6979_next's retry, which tells only that a DISCARDED
 // candidate was out of range (RFC 6979 3.2 step h.3).
@@ -18,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "der_enc_dev.h"
 #include "sha256.h"
 
 namespace mbft {
@@ -218,6 +221,26 @@ MBFT_HD void sign_pick(uint32_t (&w)[16], const uint32_t* win, int count, uint32
 #pragma unroll
     for (int k = 0; k < 16; k++) w[k] = (v[k] & m) | (w[k] & ~m);
   }
+}
+
+// ---------------------------------------------------------------------------
+// The software USIG's UI (k_usig_uis), as the reference marshals it:
+// usig.UI{Counter, Cert} is counter_be64 || cert (usig/usig.go:54-86) and the
+// SGX USIG's cert is epoch_be64 || asn1.Marshal{R, S} (usig/sgx/sgx-usig.go:
+// 143-168), so a UI is at most 8 + 8 + 72 bytes: one kUiSlot-byte slot per
+// item, the bytes after the UI zeroed.  Returns the UI's length.  (The signed
+// digest takes epoch and counter little-endian, sha256_usig_chain; the two
+// byte orders are checked on the host build, tests/csrc/usig_check.cpp.)
+constexpr int kUiSlot = 16 + kTagSlot;
+
+MBFT_HD uint32_t usig_ui_write(uint8_t* slot, uint64_t counter, uint64_t epoch, const uint32_t r[8],
+                               const uint32_t s[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    slot[j] = (uint8_t)(counter >> (56 - 8 * j));
+    slot[8 + j] = (uint8_t)(epoch >> (56 - 8 * j));
+  }
+  return 16u + der_encode_sig(slot + 16, r, s);
 }
 
 }  // namespace mbft

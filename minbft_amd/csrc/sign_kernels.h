@@ -36,4 +36,33 @@ struct SignTagArgs {
 
 hipError_t sign_tags(const SignTagArgs& a, hipStream_t st);
 
+// where a lane's message digest SHA256(m) comes from (k_usig_uis)
+enum UsigMode : int {
+  kUsigDigests = 0,  // given: n x 32 bytes
+  kUsigFlat = 1,     // raw messages msgs[msg_off[i] .. msg_off[i+1])
+  kUsigRecords = 2   // PREPARE / COMMIT records over an arena (AuthenBytes built in the kernel)
+};
+
+// One UI per lane: lane i signs SHA256(SHA256(m_i) || epoch_le64 || (first + i)_le64).
+struct UsigArgs {
+  int mode;
+  int w;                    // window of tab
+  long n;
+  uint64_t epoch, first;    // the instance's epoch; the counter of lane 0
+  const uint8_t* digests;   // kUsigDigests (4-byte aligned)
+  const uint8_t* msgs;      // kUsigFlat
+  const uint32_t* msg_off;  // kUsigFlat: n + 1
+  const mbft_msg_rec* recs; // kUsigRecords (types and fields validated by the host)
+  const uint8_t* bytes;     // kUsigRecords: the arena
+  const uint8_t* key;       // 32 B big-endian: the USIG's private key
+  const uint32_t* tab;      // the signer's generator table (window w)
+  uint8_t* uis;             // n x MBFT_UI_SLOT
+  uint8_t* ui_len;          // n (0: no usable nonce in kSignTries candidates)
+};
+
+hipError_t usig_uis(const UsigArgs& a, hipStream_t st);
+// affine d G (X || Y, 64 bytes big-endian) through the signer's uniform comb:
+// the public key of a secret d, 0 < d < N (the USIG identity)
+hipError_t sign_pubkey(const uint8_t* key, const uint32_t* tab, int w, uint8_t* xy, hipStream_t st);
+
 }  // namespace mbft_launch

@@ -55,6 +55,10 @@
 // [1, N)) is a finite point.  (tests/test_sign_host.py checks the recoding's
 // digits and this property on the host build of sign_digit.)
 //
+// The steps from the key's load to (r, s) are one device function, sign_rs,
+// shared with k_usig_uis (the software USIG's CreateUI, further down; DESIGN.md
+// 4.6) and, for the comb alone, with k_sign_pubkey.
+//
 // Plain C++ and vector stores only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -166,24 +170,15 @@ MBFT_DEV void sign_comb(jac& acc, const uint32_t k[8], const uint32_t* __restric
   }
 }
 
-}  // namespace
-
-__global__ void __launch_bounds__(256) k_sign_tags(mbft_launch::SignTagArgs A) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.n) return;
-  // digest input e and the key of the lane's role (public: the message kind)
-  uint32_t eb[8];
-  const uint8_t* key = A.key0;
-  if (A.mode == mbft_launch::kSignPrehashed) {
-    load_be_words(eb, A.e + 32 * i);
-  } else if (A.mode == mbft_launch::kSignFlat) {
-    const uint32_t a = A.msg_off[i], b = A.msg_off[i + 1];
-    quirk_e(eb, A.msgs + a, b - a);
-  } else {
-    const mbft_msg_rec m = A.recs[i];
-    record_e(eb, m, A.bytes);
-    if (m.type == MBFT_MSG_REQUEST) key = A.key1;
-  }
+// The signer both kernels share: (r, s) over the digest input eb
+// (big-endian-numeric words) under the 32-byte big-endian key at `key`, the
+// values as big-endian-numeric words.  Everything from the key's load on:
+// the nonce loop, sign_comb, the two fixed-exponent inversions, the zero
+// checks.  false (r = s = 0): none of kSignTries candidates was usable.  The
+// callers finish their hashing of public bytes before they call it, so the
+// key and what derives from it are live only here.
+MBFT_DEV bool sign_rs(uint32_t (&rb)[8], uint32_t (&sb)[8], const uint8_t* key, const uint32_t (&eb)[8],
+                      const uint32_t* tab, int W) {
   uint32_t db[8];
   load_be_words(db, key);
 
@@ -200,7 +195,8 @@ __global__ void __launch_bounds__(256) k_sign_tags(mbft_launch::SignTagArgs A) {
   for (int j = 0; j < 8; j++) q[j] = kNbe[j];
   Rfc6979 g;
   g.init(db, eb, q);
-  uint32_t rb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 8; j++) { rb[j] = 0; sb[j] = 0; }
   bool ok = false;
   int left = kSignTries;
   uint32_t kb[8];
@@ -210,7 +206,7 @@ __global__ void __launch_bounds__(256) k_sign_tags(mbft_launch::SignTagArgs A) {
 #pragma unroll
     for (int j = 0; j < 8; j++) kw[j] = kb[7 - j];
     jac R;
-    sign_comb(R, kw, A.tab, A.w);
+    sign_comb(R, kw, tab, W);
     fe zi, x;
     fe_inv(zi, R.Z);
     fe_sqr(zi, zi);
@@ -240,6 +236,29 @@ __global__ void __launch_bounds__(256) k_sign_tags(mbft_launch::SignTagArgs A) {
     }
     g.retry();  // RFC 6979 3.2 h.3 for a discarded candidate
   }
+  return ok;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_sign_tags(mbft_launch::SignTagArgs A) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  // digest input e and the key of the lane's role (public: the message kind)
+  uint32_t eb[8];
+  const uint8_t* key = A.key0;
+  if (A.mode == mbft_launch::kSignPrehashed) {
+    load_be_words(eb, A.e + 32 * i);
+  } else if (A.mode == mbft_launch::kSignFlat) {
+    const uint32_t a = A.msg_off[i], b = A.msg_off[i + 1];
+    quirk_e(eb, A.msgs + a, b - a);
+  } else {
+    const mbft_msg_rec m = A.recs[i];
+    record_e(eb, m, A.bytes);
+    if (m.type == MBFT_MSG_REQUEST) key = A.key1;
+  }
+  uint32_t rb[8], sb[8];
+  const bool ok = sign_rs(rb, sb, key, eb, A.tab, A.w);
   uint8_t* out = A.tags + (size_t)kTagSlot * i;
   if (ok) {
     A.tag_len[i] = (uint8_t)der_encode_sig(out, rb, sb);
@@ -250,7 +269,105 @@ __global__ void __launch_bounds__(256) k_sign_tags(mbft_launch::SignTagArgs A) {
   }
 }
 
+// k_usig_uis: the software USIG's CreateUI (usig/sgx/enclave/usig.c:36-76
+// ecall_usig_create_ui, reached through usig/sgx/sgx-usig.go:52-64 CreateUI),
+// one UI per lane.  Lane i holds counter first + i; epoch, counter, message
+// bytes and lengths are public, so the hash side may branch on them:
+//   SHA256(m)  given, or of a raw message (sha256_msg), or of the PREPARE /
+//              COMMIT AuthenBytes of a record (authen_dev.h: 59 / 70 bytes);
+//   e          SHA256(SHA256(m) || epoch_le64 || counter_le64) (sgx-usig.go:
+//              99-101, usig-enclave.go:204-214), one compression;
+//   (r, s)     sign_rs, the signer of k_sign_tags: the key is loaded only
+//              after e is complete, and the uniform-access property stated at
+//              the head of this file holds from there on unchanged;
+//   UI         counter_be64 || epoch_be64 || asn1.Marshal{R, S} into the lane's
+//              88-byte slot (usig_ui_write), its length into ui_len; the whole
+//              slot zeroed and length 0 when no candidate was usable.
+// The host (sign.cpp) owns the counter: it hands a range to one launch at a
+// time and advances only after every UI of the range came back.
+__global__ void __launch_bounds__(256) k_usig_uis(mbft_launch::UsigArgs A) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const uint64_t counter = A.first + (uint64_t)i;
+  uint32_t eb[8];
+  if (A.mode == mbft_launch::kUsigRecords) {
+    const mbft_msg_rec m = A.recs[i];
+    uint32_t h[8];
+    sha256_msg(h, m.op_len ? A.bytes + m.op_off : A.bytes, m.op_len);
+    authen_digest(eb, m.type == MBFT_MSG_PREPARE ? kAuthenPrepare : kAuthenCommit, h, m.seq, m.client_id,
+                  m.view, m.prep_replica_id, m.prep_ui_counter, A.epoch, counter);
+  } else {
+    uint32_t dig[8];
+    if (A.mode == mbft_launch::kUsigDigests) {
+      load_be_words(dig, A.digests + 32 * i);
+    } else {
+      const uint32_t a = A.msg_off[i], b = A.msg_off[i + 1];
+      sha256_msg(dig, A.msgs + a, b - a);
+    }
+    sha256_usig_chain(eb, dig, A.epoch, counter);
+  }
+  uint32_t rb[8], sb[8];
+  const bool ok = sign_rs(rb, sb, A.key, eb, A.tab, A.w);
+  uint8_t* out = A.uis + (size_t)kUiSlot * i;
+  if (ok) {
+    A.ui_len[i] = (uint8_t)usig_ui_write(out, counter, A.epoch, rb, sb);
+  } else {
+#pragma unroll 1
+    for (int j = 0; j < kUiSlot; j++) out[j] = 0;
+    A.ui_len[i] = 0;
+  }
+}
+
+// k_sign_pubkey: affine d G of the secret d at `key` (0 < d < N, checked by
+// the host), X || Y big-endian, for the USIG identity (sgx-usig.go:105-139:
+// the enclave's public key).  One lane; d goes through sign_comb like a
+// nonce, never through k_sign or a gather table, and 1 / Z is the
+// fixed-exponent fe_inv.  d G is finite for 0 < d < N (the comb's argument at
+// the head of this file), so Z != 0.
+__global__ void __launch_bounds__(64) k_sign_pubkey(const uint8_t* key, const uint32_t* tab, int W,
+                                                    uint8_t* xy) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t db[8], dw[8];
+  load_be_words(db, key);
+#pragma unroll
+  for (int j = 0; j < 8; j++) dw[j] = db[7 - j];
+  jac R;
+  sign_comb(R, dw, tab, W);
+  fe zi, zi2, x, y;
+  fe_inv(zi, R.Z);
+  fe_sqr(zi2, zi);
+  fe_mul(x, R.X, zi2);
+  fe_mul(zi2, zi2, zi);
+  fe_mul(y, R.Y, zi2);
+  fe_from_mont(x, x);
+  fe_canon(x);
+  fe_from_mont(y, y);
+  fe_canon(y);
+  uint32_t xw[8], yw[8];
+  fe_to_words(xw, x);
+  fe_to_words(yw, y);
+  uint32_t* o = reinterpret_cast<uint32_t*>(xy);
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    o[j] = __builtin_bswap32(xw[7 - j]);
+    o[8 + j] = __builtin_bswap32(yw[7 - j]);
+  }
+}
+
 namespace mbft_launch {
+
+hipError_t usig_uis(const UsigArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.w < kSignMinWindow || a.w > kSignMaxWindow) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_usig_uis, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t sign_pubkey(const uint8_t* key, const uint32_t* tab, int w, uint8_t* xy, hipStream_t st) {
+  if (w < kSignMinWindow || w > kSignMaxWindow) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sign_pubkey, dim3(1), dim3(64), 0, st, key, tab, w, xy);
+  return hipGetLastError();
+}
 
 hipError_t sign_tags(const SignTagArgs& a, hipStream_t st) {
   if (a.n <= 0) return hipSuccess;
