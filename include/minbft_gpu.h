@@ -230,7 +230,7 @@ int mbft_set_resident(mbft_ctx* ctx, int slots);
 /* out[6]: slots, calls served, kernel launches, calls that found every slot
  * taken, relaunches found by a stream query, 1 if the kernel's stream has
  * its own hardware queue (the lowest stream priority, which no other stream
- * of the library uses; or CU-masked with MBFT_RESIDENT_CUMASK=1). */
+ * of the library uses). */
 int mbft_resident_stats(mbft_ctx* ctx, double out[6]);
 /* out[5] (new, round 6): the caller-side wait of resident calls -- sleeps
  * taken, sleeps that woke after the items were done, the current estimates
@@ -329,7 +329,7 @@ int mbft_set_small_batch_form(mbft_ctx* ctx, long split_max);
  * inversion per 16 items); 3 the batched per-wave s^-1 into planes first
  * (k_ninv_local), then k_verify_quads; 1 the planes, then k_verify_pairs (an
  * item per lane pair); 0 k_verify_pairs inverting s per lane (divsteps); -1
- * env MBFT_PAIRS_PLANES / MBFT_QUADS / MBFT_QUADS_INLINE (default 2).
+ * the default (2).
  * MBFT_ERR_ARG outside -1..3. */
 int mbft_set_small_batch_inverse(mbft_ctx* ctx, int mode);
 /* Two-phase form of the same semantics, for callers that must keep their

@@ -52,8 +52,8 @@ constexpr size_t kParallelMin = 4096;
 constexpr size_t kParallelGrain = 128;
 int host_threads_for(const mbft_ctx* g, size_t n) {
   static const size_t lo = [] {
-    const char* v = getenv("MBFT_PARALLEL_MIN");
-    return v && atol(v) > 0 ? (size_t)atol(v) : kParallelMin;
+    const long v = mbft::env_long("MBFT_PARALLEL_MIN", 0);
+    return v > 0 ? (size_t)v : kParallelMin;
   }();
   if (n < lo) return 1;
   const size_t t = n / kParallelGrain;
@@ -82,22 +82,15 @@ constexpr size_t kHostInvMax = 64;
 // paths do not have.
 size_t host_inv_max() {
   static const size_t v = [] {
-    const char* e = getenv("MBFT_HOST_INV_MAX");
-    const size_t x = e ? (size_t)strtoull(e, nullptr, 10) : kHostInvMax;
+    const size_t x = mbft::env_size("MBFT_HOST_INV_MAX", kHostInvMax);
     return x < kZeroCopyMax ? x : kZeroCopyMax;
   }();
   return v;
 }
 
 // The engine's zero-copy staging, allocated on first use; false when the
-// platform cannot map it (then the copy path is used).  Env
-// MBFT_ZERO_COPY=0 disables it.
+// platform cannot map it (then the copy path is used).
 bool zero_copy_ready(mbft_ctx* g) {
-  static const bool off = [] {
-    const char* v = getenv("MBFT_ZERO_COPY");
-    return v && atoi(v) == 0;
-  }();
-  if (off) return false;
   if (g->zc_state == 0) {
     g->zc_state = -1;
     void* h = nullptr;
@@ -128,10 +121,7 @@ bool zero_copy_ready(mbft_ctx* g) {
 // after writing its statuses is reported by this call, not a later one.
 constexpr uint8_t kStatusPending = 0xFF;
 bool spin_statuses(mbft_ctx* g, const uint8_t* st, size_t n) {
-  static const double spin_env = [] {
-    const char* v = getenv("MBFT_SPIN_US");
-    return v ? atof(v) / 1000.0 : -1.0;
-  }();
+  static const double spin_env = mbft::env_double("MBFT_SPIN_US", -1.0) / 1000.0;  // ms; unset: negative
   (void)g;
   const double spin_ms = spin_env >= 0 ? spin_env : 0.3 + 0.004 * (double)n;
   if (spin_ms <= 0) return false;
@@ -300,10 +290,9 @@ bool prepare_item(const mbft_ctx* c, const mbft_item& it, CallInfo& p, uint8_t* 
 
 int host_pool_threads() {
   static const int n = [] {
-    for (const char* k : {"MBFT_HOST_THREADS", "OMP_NUM_THREADS"}) {
-      const char* v = getenv(k);
-      if (v && atoi(v) > 0) return atoi(v) > 64 ? 64 : atoi(v);
-    }
+    const int set[] = {(int)mbft::env_long("MBFT_HOST_THREADS", 0), (int)mbft::env_long("OMP_NUM_THREADS", 0)};
+    for (const int v : set)
+      if (v > 0) return v > 64 ? 64 : v;
     const unsigned h = std::thread::hardware_concurrency();
     return h == 0 ? 1 : (h > 32 ? 32 : (int)h);
   }();
@@ -321,19 +310,14 @@ namespace {
 // profiles/round2_auth_sweep.jsonl) -- GPU decode 5.3 ms at 128K, 4.4 at
 // 256K, 4.7 at 512K, 5.5 as one chunk; host decode 7.0 / 5.2 / 6.6 ms.
 size_t chunk_items(size_t n) {
-  const char* v = getenv("MBFT_BATCH_CHUNK");
-  const size_t ck = v ? (size_t)strtoull(v, nullptr, 10) : (size_t)1 << 18;
+  const size_t ck = mbft::env_size("MBFT_BATCH_CHUNK", (size_t)1 << 18);
   return ck == 0 ? n : ck;
 }
 
 // Chunk sizes of a GPU-decode batch of n calls (chunks of ck).  After the
 // last copy only the last chunks' decode, s^-1 and verify remain on the
-// critical path, so the batch ends in a shorter chunk.  Env MBFT_TAIL_FORM:
-//   short    (default) one last chunk of ck / MBFT_TAIL_DIV (default 4);
-//   geo      ck / 2, ck / 4, ... down to MBFT_TAIL_MIN (default 4096: a
-//            chunk that small takes the per-lane inverse, no chain), the
-//            main part's remainder first.  Measured 0.5 ms slower per 1M
-//            batch than `short`: kept for the record.
+// critical path, so the batch ends in one shorter chunk of ck /
+// MBFT_TAIL_DIV (default 4; 0: no shorter chunk).
 // Env MBFT_TAIL_LOCAL = how many of the last chunks take the one-launch
 // s^-1 on their own stream instead of the level chain (default 1: no later
 // chunk to hide a five-launch chain behind; 3.95/3.82 -> 3.73/3.79 ms).
@@ -343,48 +327,22 @@ std::vector<size_t> chunk_plan(size_t n, size_t ck) {
     out.push_back(n);
     return out;
   }
-  const char* form = getenv("MBFT_TAIL_FORM");
-  if (!(form && strcmp(form, "geo") == 0)) {
-    const char* dv = getenv("MBFT_TAIL_DIV");
-    const size_t div = dv ? (size_t)strtoull(dv, nullptr, 10) : 4;
-    const size_t tail = div ? ck / div : 0;
-    for (size_t lo = 0, m = 0; lo < n; lo += m) {
-      const size_t rem = n - lo;
-      m = rem > ck + tail ? ck : (rem > 2 * tail && tail > 0 ? rem - tail : rem);
-      out.push_back(m);
-    }
-    return out;
+  const size_t div = mbft::env_size("MBFT_TAIL_DIV", 4);
+  const size_t tail = div ? ck / div : 0;
+  for (size_t lo = 0, m = 0; lo < n; lo += m) {
+    const size_t rem = n - lo;
+    m = rem > ck + tail ? ck : (rem > 2 * tail && tail > 0 ? rem - tail : rem);
+    out.push_back(m);
   }
-  const char* tv = getenv("MBFT_TAIL_MIN");
-  const size_t tmin = std::max<size_t>(tv ? (size_t)strtoull(tv, nullptr, 10) : 4096, 256);
-  std::vector<size_t> tail;
-  size_t sum = 0;
-  for (size_t t = ck / 2; t >= tmin && sum + t + ck <= n; t /= 2) {
-    tail.push_back(t);
-    sum += t;
-  }
-  const size_t main = n - sum;
-  if (main % ck) out.push_back(main % ck);
-  for (size_t j = 0; j < main / ck; j++) out.push_back(ck);
-  out.insert(out.end(), tail.begin(), tail.end());
   return out;
 }
 
-bool tail_prio() {
-  const char* v = getenv("MBFT_TAIL_PRIO");
-  return v && atoi(v) != 0;
-}
-
-int tail_local() {
-  const char* v = getenv("MBFT_TAIL_LOCAL");
-  return v ? atoi(v) : 1;
-}
+int tail_local() { return (int)mbft::env_long("MBFT_TAIL_LOCAL", 1); }
 
 // copy streams the chunks' H2D copies alternate over (env MBFT_COPY_STREAMS,
 // read per batch: 1 or 2)
 int copy_streams() {
-  const char* v = getenv("MBFT_COPY_STREAMS");
-  return v && atoi(v) == 2 ? 2 : 1;
+  return (int)mbft::env_long("MBFT_COPY_STREAMS", 1) == 2 ? 2 : 1;
 }
 
 // A worker's deferred USIG digest (GPU SHA stage): call i, its UI fields.
@@ -718,7 +676,7 @@ int engine_check(mbft_ctx* c, mbft_ctx* g, const Src& src, size_t base, size_t n
     const size_t a = n * t / T, b = n * (t + 1) / T;
     memcpy(gst + a, hst + a, b - a);
   });
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   if (trace)
     fprintf(stderr, "[mbft stage] n=%zu T=%d chunks=%d prep=%.3f enqueue+prep=%.3f wait=%.3f copy=%.3f ms\n",
             n, T, k, t_prep, t1 - t_start, t2 - t1, now_ms() - t2);
@@ -842,14 +800,8 @@ int engine_check_dev(mbft_ctx* c, mbft_ctx* g, const FlatItems& src, size_t base
   const int nlocal = tail_local();
   // The four per-call arrays (roles, ids, offsets: 24 B per call) go up whole
   // before the first chunk's bytes when the batch is chunked: each copy costs
-  // the DMA engine ~10 us of setup, so 4 copies instead of 4 per chunk (env
-  // MBFT_SMALL_FIRST=0: per chunk, as the bytes).
-  static const bool small_first = [] {
-    const char* v = getenv("MBFT_SMALL_FIRST");
-    return !(v && atoi(v) == 0);
-  }();
-  const bool upfront = small_first && plan.size() > 1;
-  bool used_prio = false;
+  // the DMA engine ~10 us of setup, so 4 copies instead of 4 per chunk.
+  const bool upfront = plan.size() > 1;
   // device copies of the per-call arrays keep the caller's widths
   const void* roles_src = src.compact() ? (const void*)src.roles8 : (const void*)src.roles;
   const void* moff_src = src.compact() ? (const void*)src.msg_off32 : (const void*)src.msg_off;
@@ -929,21 +881,10 @@ int engine_check_dev(mbft_ctx* c, mbft_ctx* g, const FlatItems& src, size_t base
     a.r = g->b_r.as<uint8_t>() + 32 * lo;
     a.s = g->b_s.as<uint8_t>() + 32 * lo;
     a.slot = g->b_slot.as<uint32_t>() + lo;
-    // MBFT_TAIL_PRIO: the latency chunks' decode, s^-1, verify and statuses
-    // on the high-priority stream, so their workgroups are dispatched ahead of
-    // the previous chunk's remaining verify workgroups
-    const bool prio = latency && tail_prio();
-    hipStream_t vs = prio ? g->istream : g->vstream[k & 1];
-    if (prio) {
-      HIPCHK(g, hipEventRecord(evh, cs));
-      HIPCHK(g, hipStreamWaitEvent(vs, evh, 0));
-      HIPCHK(g, mbft_launch::prepare_calls(a, vs));
-    } else {
-      HIPCHK(g, mbft_launch::prepare_calls(a, cs));
-      HIPCHK(g, hipEventRecord(evh, cs));
-      HIPCHK(g, hipStreamWaitEvent(vs, evh, 0));
-    }
-    used_prio |= prio;
+    hipStream_t vs = g->vstream[k & 1];
+    HIPCHK(g, mbft_launch::prepare_calls(a, cs));
+    HIPCHK(g, hipEventRecord(evh, cs));
+    HIPCHK(g, hipStreamWaitEvent(vs, evh, 0));
     rc = verify_device(g, a.e, a.r, a.s, a.slot, m, g->b_status.as<uint8_t>() + lo, vs,
                        /*host_status=*/true, latency);
     if (rc) return rc;
@@ -958,7 +899,6 @@ int engine_check_dev(mbft_ctx* c, mbft_ctx* g, const FlatItems& src, size_t base
   const double t1 = now_ms();
   HIPCHK(g, hipStreamSynchronize(g->vstream[0]));
   HIPCHK(g, hipStreamSynchronize(g->vstream[1]));
-  if (used_prio) HIPCHK(g, hipStreamSynchronize(g->istream));
   const double t2 = now_ms();
   g->pool->wait();
   if (host_bad || *g->hm_bad.as<uint32_t>() != 0)
@@ -972,7 +912,7 @@ int engine_check_dev(mbft_ctx* c, mbft_ctx* g, const FlatItems& src, size_t base
       memcpy(gst + a, hst + a, b - a);
     });
   }
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   if (trace)
     fprintf(stderr, "[mbft stage dev] n=%zu chunks=%d enqueue=%.3f wait=%.3f usig+copy=%.3f ms\n", n,
             k, t1 - t_start, t2 - t1, now_ms() - t2);
@@ -1270,8 +1210,7 @@ void signal_waiter(mbft_ctx::Waiter& x) {
 // MBFT_COALESCE_SPIN_US, default 200; 0: it sleeps like the others).
 double coalesce_spin_us() {
   static const double v = [] {
-    const char* e = getenv("MBFT_COALESCE_SPIN_US");
-    return e ? atof(e) : 200.0;
+    return mbft::env_double("MBFT_COALESCE_SPIN_US", 200.0);
   }();
   return v;
 }

@@ -58,8 +58,7 @@ void segv_trace(int sig, siginfo_t* si, void* uc) {
 }
 struct SegvInit {
   SegvInit() {
-    const char* v = getenv("MBFT_SEGV_TRACE");
-    if (v && atoi(v)) {
+    if (mbft::env_on("MBFT_SEGV_TRACE", false)) {
       struct sigaction sa;
       memset(&sa, 0, sizeof sa);
       sa.sa_sigaction = segv_trace;
@@ -99,10 +98,7 @@ int device_numa_node(int d) {
 }  // namespace
 
 hipError_t host_malloc_near(void** p, size_t bytes, unsigned flags) {
-  static const bool off = [] {
-    const char* v = getenv("MBFT_NUMA_STAGING");
-    return v && atoi(v) == 0;
-  }();
+  static const bool off = !mbft::env_on("MBFT_NUMA_STAGING", true);
   int dev = 0;
   const int node = off || hipGetDevice(&dev) != hipSuccess ? -1 : device_numa_node(dev);
   if (node < 0 || node >= 64) return hipHostMalloc(p, bytes, flags);
@@ -342,10 +338,7 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
   // Small batches: no batched s^-1 chain (five dependent launches, ~180 us
   // of latency); k_verify_pairs inverts s per lane (divsteps, modinv.h).
   // Env MBFT_LANE_INV_MAX (default 4096 items; 0 disables).
-  static const size_t lane_inv_max = [] {
-    const char* v = getenv("MBFT_LANE_INV_MAX");
-    return v ? (size_t)strtoull(v, nullptr, 10) : (size_t)4096;
-  }();
+  static const size_t lane_inv_max = mbft::env_size("MBFT_LANE_INV_MAX", 4096);
   // d_count: n is an upper bound, the count is on the device -- the small-batch
   // kernels, which read it (no batched chain: it is sized by n on the host)
   const bool small = n <= lane_inv_max || d_count;
@@ -358,62 +351,52 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
     HIPCHK(c, hipEventCreate(&ev.d));
     ev.n = n;
   }
+  // Every path ends the same way on the caller's stream: the verify over w
+  // planes `winv` (null: the small-batch forms, which alone read split_max,
+  // d_count, the planes workspace and small_inv), then ev_done[k].  Profiling
+  // brackets it with ev.c and ev.d; ev.a and ev.b (the s^-1 span) are each
+  // path's own.
+  auto verify_and_mark_done = [&](const uint32_t* winv, bool queue_zeroed) -> int {
+    if (c->prof) HIPCHK(c, hipEventRecord(ev.c, st));
+    HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, winv, tb->d_tabG, tb->g_wbits,
+                                  tb->d_keys.as<mbft::KeyDesc>(), (uint32_t)tb->slots.size(),
+                                  (long)n, d_status, c->slowq[k].as<uint32_t>(), st, host_status,
+                                  queue_zeroed, tb->split_max, /*split_winv=*/d_winv != nullptr,
+                                  d_count, /*planes_ws=*/d_winv ? nullptr : c->winv[k].as<uint32_t>(),
+                                  tb->small_inv));
+    HIPCHK(c, hipEventRecord(c->ev_done[k], st));
+    if (c->prof) {
+      HIPCHK(c, hipEventRecord(ev.d, st));
+      c->evs.push_back(ev);
+    }
+    return MBFT_OK;
+  };
   if (small || d_winv) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // slowq[k] reuse
     if (c->prof) {
       HIPCHK(c, hipEventRecord(ev.a, st));
       HIPCHK(c, hipEventRecord(ev.b, st));
-      HIPCHK(c, hipEventRecord(ev.c, st));
     }
-    HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, d_winv, tb->d_tabG, tb->g_wbits,
-                                  tb->d_keys.as<mbft::KeyDesc>(), (uint32_t)tb->slots.size(),
-                                  (long)n, d_status, c->slowq[k].as<uint32_t>(), st, host_status,
-                                  /*queue_zeroed=*/false, tabs(c)->split_max,
-                                  /*split_winv=*/d_winv != nullptr, d_count,
-                                  /*planes_ws=*/d_winv ? nullptr : c->winv[k].as<uint32_t>(),
-                                  tabs(c)->small_inv));
-    HIPCHK(c, hipEventRecord(c->ev_done[k], st));
-    if (c->prof) {
-      HIPCHK(c, hipEventRecord(ev.d, st));
-      c->evs.push_back(ev);
-    }
-    return MBFT_OK;
+    return verify_and_mark_done(d_winv, /*queue_zeroed=*/false);
   }
-  // A batch issued while every earlier batch of this engine has finished
-  // (one batch at a time: its latency counts) takes the one-launch s^-1
-  // (k_ninv_local) on the caller's stream, no cross-stream hand-off; while
-  // earlier batches are in flight the level chain runs on the high-priority
-  // stream beside them, hidden, with less VALU work.  Env
-  // MBFT_NINV = local | levels forces one form.  `latency` (a pipeline's
-  // last chunks, nothing after them to hide a chain behind) takes the
-  // one-launch form in any case, once buffer k is free.
-  // Diagnostic only (never set by the bench line): MBFT_DIAG_REUSE_WINV=1
-  // skips the s^-1 kernels once buffer k holds a batch's w planes, for
-  // callers that verify the SAME batch again through the prehashed device
-  // entry (the s^-1 stage's share of a step, tools/streams_ab.sh).
-  static const bool diag_reuse = getenv("MBFT_DIAG_REUSE_WINV") != nullptr;
-  if (diag_reuse && !host_status && c->diag_winv_n[k] == n) {
-    HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));
-    if (c->prof) {
-      HIPCHK(c, hipEventRecord(ev.a, st));
-      HIPCHK(c, hipEventRecord(ev.b, st));
-      HIPCHK(c, hipEventRecord(ev.c, st));
-    }
-    HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, c->winv[k].as<uint32_t>(), tb->d_tabG,
-                                  tb->g_wbits, tb->d_keys.as<mbft::KeyDesc>(),
-                                  (uint32_t)tb->slots.size(), (long)n, d_status,
-                                  c->slowq[k].as<uint32_t>(), st, host_status, /*queue_zeroed=*/false));
-    HIPCHK(c, hipEventRecord(c->ev_done[k], st));
-    if (c->prof) {
-      HIPCHK(c, hipEventRecord(ev.d, st));
-      c->evs.push_back(ev);
-    }
-    return MBFT_OK;
-  }
-  if (diag_reuse && !host_status) c->diag_winv_n[k] = n;
-  const char* ninv = getenv("MBFT_NINV");
-  bool idle = !(ninv && strcmp(ninv, "levels") == 0);
-  if (idle && !(ninv && strcmp(ninv, "local") == 0))
+  // The batched s^-1 has three forms:
+  //  1. every earlier batch of this engine has finished (one batch at a time:
+  //     its latency counts): one launch, k_ninv_block<8>, on the caller's
+  //     stream, no cross-stream hand-off;
+  //  2. earlier batches in flight (the pipelined loop): one launch,
+  //     k_ninv_local<16>, on the caller's stream once buffer k is free -- its
+  //     waves interleave with the previous batch's verify waves (0.954
+  //     against 1.048 ms a step with the level chain, same box,
+  //     profiles/round6_ninv_forms.jsonl);
+  //  3. MBFT_NINV=levels: the level chain (k_ninv_up / k_ninv_top /
+  //     k_ninv_down) on the high-priority stream beside the earlier batches
+  //     (round 5's default), whether or not any is in flight.
+  // MBFT_NINV=local takes form 1 without asking whether the GPU is idle.
+  // `latency` (a pipeline's last chunks, nothing after them to hide a chain
+  // behind) takes form 1 in any case, once buffer k is free.
+  const bool levels = mbft::env_is("MBFT_NINV", "levels");
+  bool idle = !levels;
+  if (idle && !mbft::env_is("MBFT_NINV", "local"))
     for (int j = 0; j < mbft_ctx::kPipe && idle; j++) {
       const hipError_t q = hipEventQuery(c->ev_done[j]);
       if (q == hipErrorNotReady) {
@@ -426,88 +409,21 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // winv[k] / slowq[k] reuse
     idle = true;
   }
-  // Split idle batch (env MBFT_SPLIT_DIV = d >= 2; off by default, and never
-  // while profiling, which times whole kernels): part 0 (the first n / d
-  // items) inverts and verifies on the caller's stream, part 1 inverts on the
-  // library stream at the same time and verifies there as soon as its
-  // inverse is done, so the larger part's s^-1 runs beside part 0's verify
-  // instead of before it.  Each part has its own w planes, exact-path queue
-  // and spill planes; the caller's stream joins part 1 before anything reads
-  // the statuses.  Measured no better than one launch of each (two
-  // concurrent verify grids lose ~40 us to their tails).
-  static const long split_div = [] {
-    const char* v = getenv("MBFT_SPLIT_DIV");
-    return v ? atol(v) : 0L;
-  }();
-  if (idle && !c->prof && split_div >= 2 && n >= 65536) {
-    const size_t n0 = (((size_t)n / (size_t)split_div) + 255) & ~(size_t)255, n1 = n - n0;
-    const size_t q0 = mbft_launch::verify_words((long)n0, false);
-    HIPCHK(c, c->slowq[k].ensure((q0 + mbft_launch::verify_words((long)n1, false)) * 4));
-    uint32_t* w = c->winv[k].as<uint32_t>();
-    uint32_t* q = c->slowq[k].as<uint32_t>();
-    HIPCHK(c, hipEventRecord(c->ev_in, st));
-    HIPCHK(c, hipStreamWaitEvent(c->istream, c->ev_in, 0));
-    HIPCHK(c, mbft_launch::batch_inverse_s_local(d_s, (long)n0, w, q + n0, st));
-    HIPCHK(c, mbft_launch::batch_inverse_s_local(d_s + 32 * n0, (long)n1, w + 9 * n0, q + q0 + n1,
-                                                 c->istream));
-    HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, w, tb->d_tabG, tb->g_wbits,
-                                  tb->d_keys.as<mbft::KeyDesc>(), (uint32_t)tb->slots.size(),
-                                  (long)n0, d_status, q, st, host_status, /*queue_zeroed=*/true));
-    HIPCHK(c, mbft_launch::verify(d_e + 32 * n0, d_r + 32 * n0, d_s + 32 * n0, d_slot + n0,
-                                  w + 9 * n0, tb->d_tabG, tb->g_wbits,
-                                  tb->d_keys.as<mbft::KeyDesc>(), (uint32_t)tb->slots.size(),
-                                  (long)n1, d_status + n0, q + q0, c->istream, host_status,
-                                  /*queue_zeroed=*/true));
-    HIPCHK(c, hipEventRecord(c->ev_inv[k], c->istream));
-    HIPCHK(c, hipStreamWaitEvent(st, c->ev_inv[k], 0));
-    HIPCHK(c, hipEventRecord(c->ev_done[k], st));
-    return MBFT_OK;
-  }
+  // (each form's last kernel also zeroes the verify's exact-path queue counter)
+  uint32_t* const winv = c->winv[k].as<uint32_t>();
+  uint32_t* const qlen = c->slowq[k].as<uint32_t>() + n;
   if (idle) {
     if (c->prof) HIPCHK(c, hipEventRecord(ev.a, st));
-    // (the kernel also zeroes the verify's exact-path queue counter)
-    HIPCHK(c, mbft_launch::batch_inverse_s_local(d_s, (long)n, c->winv[k].as<uint32_t>(),
-                                                 c->slowq[k].as<uint32_t>() + n, st));
-    if (c->prof) {
-      HIPCHK(c, hipEventRecord(ev.b, st));
-      HIPCHK(c, hipEventRecord(ev.c, st));
-    }
-    HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, c->winv[k].as<uint32_t>(), tb->d_tabG,
-                                  tb->g_wbits, tb->d_keys.as<mbft::KeyDesc>(),
-                                  (uint32_t)tb->slots.size(), (long)n, d_status,
-                                  c->slowq[k].as<uint32_t>(), st, host_status, /*queue_zeroed=*/true));
-    HIPCHK(c, hipEventRecord(c->ev_done[k], st));
-    if (c->prof) {
-      HIPCHK(c, hipEventRecord(ev.d, st));
-      c->evs.push_back(ev);
-    }
-    return MBFT_OK;
+    HIPCHK(c, mbft_launch::batch_inverse_s_local(d_s, (long)n, winv, qlen, st));
+    if (c->prof) HIPCHK(c, hipEventRecord(ev.b, st));
+    return verify_and_mark_done(winv, /*queue_zeroed=*/true);
   }
-  // Earlier batches in flight (the pipelined loop): the one-launch per-wave
-  // s^-1 on the caller's stream, right before the verify, once buffer k is
-  // free -- its waves interleave with the previous batch's verify waves
-  // (0.954 against 1.048 ms a step with the level chain below, same box,
-  // profiles/round6_ninv_forms.jsonl).  MBFT_NINV=levels: the level chain on
-  // the high-priority stream (round 5).
-  if (!(ninv && strcmp(ninv, "levels") == 0)) {
+  if (!levels) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // winv[k] / slowq[k] reuse
     if (c->prof) HIPCHK(c, hipEventRecord(ev.a, st));
-    HIPCHK(c, mbft_launch::batch_inverse_s_pipelined(d_s, (long)n, c->winv[k].as<uint32_t>(),
-                                                     c->slowq[k].as<uint32_t>() + n, st));
-    if (c->prof) {
-      HIPCHK(c, hipEventRecord(ev.b, st));
-      HIPCHK(c, hipEventRecord(ev.c, st));
-    }
-    HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, c->winv[k].as<uint32_t>(), tb->d_tabG,
-                                  tb->g_wbits, tb->d_keys.as<mbft::KeyDesc>(),
-                                  (uint32_t)tb->slots.size(), (long)n, d_status,
-                                  c->slowq[k].as<uint32_t>(), st, host_status, /*queue_zeroed=*/true));
-    HIPCHK(c, hipEventRecord(c->ev_done[k], st));
-    if (c->prof) {
-      HIPCHK(c, hipEventRecord(ev.d, st));
-      c->evs.push_back(ev);
-    }
-    return MBFT_OK;
+    HIPCHK(c, mbft_launch::batch_inverse_s_pipelined(d_s, (long)n, winv, qlen, st));
+    if (c->prof) HIPCHK(c, hipEventRecord(ev.b, st));
+    return verify_and_mark_done(winv, /*queue_zeroed=*/true);
   }
   // inputs ready on the caller's stream; buffer k free once the verify that
   // last read it (two calls ago) has finished
@@ -515,28 +431,15 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
   HIPCHK(c, hipStreamWaitEvent(c->istream, c->ev_in, 0));
   HIPCHK(c, hipStreamWaitEvent(c->istream, c->ev_done[k], 0));
   if (c->prof) HIPCHK(c, hipEventRecord(ev.a, c->istream));
-  // (the chain's last kernel also zeroes the verify's exact-path queue counter:
-  // slowq[k] is free, the chain waited for ev_done[k])
-  HIPCHK(c, mbft_launch::batch_inverse_s(d_s, (long)n, c->ws[k].as<uint32_t>(),
-                                         c->winv[k].as<uint32_t>(),
-                                         c->slowq[k].as<uint32_t>() + n, c->istream));
+  // (slowq[k] is free: the chain waited for ev_done[k])
+  HIPCHK(c, mbft_launch::batch_inverse_s(d_s, (long)n, c->ws[k].as<uint32_t>(), winv, qlen, c->istream));
   if (c->prof) HIPCHK(c, hipEventRecord(ev.b, c->istream));
   HIPCHK(c, hipEventRecord(c->ev_inv[k], c->istream));
   HIPCHK(c, hipStreamWaitEvent(st, c->ev_inv[k], 0));
   // slowq[k]: free once the verify that last used it has finished (it may
   // have run on another stream)
   HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));
-  if (c->prof) HIPCHK(c, hipEventRecord(ev.c, st));
-  HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, c->winv[k].as<uint32_t>(), tb->d_tabG,
-                                tb->g_wbits, tb->d_keys.as<mbft::KeyDesc>(),
-                                (uint32_t)tb->slots.size(), (long)n, d_status,
-                                c->slowq[k].as<uint32_t>(), st, host_status, /*queue_zeroed=*/true));
-  HIPCHK(c, hipEventRecord(c->ev_done[k], st));
-  if (c->prof) {
-    HIPCHK(c, hipEventRecord(ev.d, st));
-    c->evs.push_back(ev);
-  }
-  return MBFT_OK;
+  return verify_and_mark_done(winv, /*queue_zeroed=*/true);
 }
 
 // Host buffers in, host status out, on ONE engine.
@@ -618,8 +521,7 @@ int verify_host(mbft_ctx* c, const uint8_t* e, const uint8_t* r, const uint8_t* 
 }
 
 size_t gpu_usig_min_calls() {
-  const char* v = getenv("MBFT_GPU_USIG_MIN_CALLS");
-  return v ? (size_t)strtoull(v, nullptr, 10) : 4096;
+  return mbft::env_size("MBFT_GPU_USIG_MIN_CALLS", 4096);
 }
 
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/minbft_gpu.h"
+#include "env.h"
 #include "kernels.h"
 #include "sign_kernels.h"
 #include "sha256.h"
@@ -481,8 +482,8 @@ struct mbft_ctx {
   // batches up to this size take k_verify_split, larger small ones k_verify_pairs
   // (mbft_set_small_batch_form; -1: env MBFT_SPLIT_MAX, default 256)
   long split_max = -1;
-  // the larger small batches' form (mbft_set_small_batch_inverse): -1 env
-  // MBFT_PAIRS_PLANES / MBFT_QUADS, 0 k_verify_pairs inverting per lane, 1 the
+  // the larger small batches' form (mbft_set_small_batch_inverse): -1 the
+  // default (2), 0 k_verify_pairs inverting per lane, 1 the
   // batched per-wave s^-1 into planes first, then k_verify_pairs, 2
   // k_verify_quads inverting per wave inside, 3 the planes and k_verify_quads
   int small_inv = -1;
@@ -577,9 +578,6 @@ struct mbft_ctx {
   double prof_verify_ms = 0, prof_inv_ms = 0, prof_batches = 0, prof_items = 0;
   // device message layer (mbft_profile_msg_layer): calls, H2D ms, device ms, bytes up
   double prof_msg[4] = {0, 0, 0, 0};
-  // MBFT_DIAG_REUSE_WINV (host.cpp verify_device): batch size whose w planes
-  // buffer k holds
-  size_t diag_winv_n[kPipe] = {};
 };
 
 namespace mbft_host {

@@ -25,6 +25,7 @@
 #include "authen_dev.h"
 #include "der_dev.h"
 #include "ecc.h"
+#include "env.h"
 
 #include "kernels.h"
 #include "modinv.h"
@@ -327,90 +328,6 @@ __global__ void k_ninv_up(const uint32_t* __restrict__ x, const uint8_t* __restr
     fn_mul(acc, acc, v);
   }
   plane_store(tot, G, g, acc);
-}
-
-// Level 0 of the chain with TWO chains per thread (chains h and h + H, H =
-// ceil(G / 2)), walked in lockstep with branch-free steps so the two
-// independent products can interleave: the same outputs as k_ninv_up<true>
-// with half the waves.  The idea: the chain kernels run beside the previous
-// batches' verify waves (3 per SIMD, 168 VGPRs), where every chain wave
-// displaces a verify wave while it lives.  Measured slower (the chain span
-// grew 0.30 -> 0.355 ms, the step 1.4 %), so off by default
-// (MBFT_NINV_CHAINS=2).  A chain's items: g, g + G, ... < n;
-// chain h is never shorter than chain h + H.
-__global__ void k_ninv_up2(const uint8_t* __restrict__ s, long n, long G, uint32_t* __restrict__ pre,
-                           uint32_t* __restrict__ tot) {
-  MBFT_CHAIN_PRIO();
-  const long H = (G + 1) / 2;
-  const long h = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= H || h >= n) return;
-  const long g1 = h + H;
-  const bool has1 = g1 < G && g1 < n;
-  fe a0, a1;
-  fe_set(a0, kRN);
-  fe_set(a1, kRN);
-#pragma unroll 1
-  for (long i0 = h; i0 < n; i0 += G) {
-    const long i1 = i0 + H;
-    const bool v1 = has1 && i1 < n;
-    fe x0, x1, t0, t1;
-    s_plain(x0, s, i0);
-    s_plain(x1, s, v1 ? i1 : i0);
-    plane_store(pre, n, i0, a0);
-    if (v1) plane_store(pre, n, i1, a1);
-    fn_mul(t0, a0, x0);
-    fn_mul(t1, a1, x1);
-    a0 = t0;
-#pragma unroll
-    for (int k = 0; k < NL; k++) a1.v[k] = v1 ? t1.v[k] : a1.v[k];
-  }
-  plane_store(tot, G, h, a0);
-  if (has1) plane_store(tot, G, g1, a1);
-}
-
-// Level 0's down-sweep with two chains per thread (k_ninv_up2's pairing):
-// each chain walked from its last item back, in lockstep (chain h + H may be
-// one item shorter: its step is then skipped).
-__global__ void k_ninv_down2(const uint8_t* __restrict__ s, const uint32_t* __restrict__ pre, long n,
-                             long G, const uint32_t* __restrict__ inv_tot, uint32_t* __restrict__ inv,
-                             uint32_t* __restrict__ zero_word) {
-  MBFT_CHAIN_PRIO();
-  if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;
-  const long H = (G + 1) / 2;
-  const long h = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= H || h >= n) return;
-  const long g1 = h + H;
-  const bool has1 = g1 < G && g1 < n;
-  fe r0, r1;
-  plane_load(r0, inv_tot, G, h);
-  if (has1) plane_load(r1, inv_tot, G, g1);
-  else fe_set(r1, kRN);
-  const long last0 = h + ((n - 1 - h) / G) * G;
-  const long len0 = (last0 - h) / G + 1;
-  const long len1 = has1 ? (n - 1 - g1) / G + 1 : 0;
-  // step k: chain 0 at last0 - k G; chain 1 at its last - (k - (len0 - len1)) G
-  const long skew = len0 - len1;  // 0 or 1
-#pragma unroll 1
-  for (long k = 0; k < len0; k++) {
-    const long i0 = last0 - k * G;
-    const long k1 = k - skew;
-    const bool v1 = has1 && k1 >= 0;
-    const long i1 = v1 ? g1 + (len1 - 1 - k1) * G : i0;
-    fe p0, p1, x0, x1, t0, t1, u0, u1;
-    plane_load(p0, pre, n, i0);
-    plane_load(p1, pre, n, i1);
-    s_plain(x0, s, i0);
-    s_plain(x1, s, i1);
-    fn_mul(t0, r0, p0);
-    fn_mul(t1, r1, p1);
-    fn_mul(u0, r0, x0);
-    fn_mul(u1, r1, x1);
-    plane_store(inv, n, i0, t0);
-    if (v1) plane_store(inv, n, i1, t1);
-    r0 = u0;
-#pragma unroll
-    for (int q = 0; q < NL; q++) r1.v[q] = v1 ? u1.v[q] : r1.v[q];
-  }
 }
 
 // The root of the tree: the m <= kTopMax chain totals x_k of the top level
@@ -2996,11 +2913,7 @@ hipError_t usig_e(const uint8_t* data, const uint64_t* off, const uint64_t* epoc
 hipError_t request_e(const uint64_t* seq, const uint8_t* ops, uint32_t op_len, long n, uint8_t* e,
                      hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  static const bool tiled = [] {
-    const char* v = getenv("MBFT_REQUEST_TILED");
-    return !(v && atoi(v) == 0);
-  }();
-  if (tiled && op_len > 0 && op_len % 16 == 0 && op_len <= (uint32_t)kReqTileMax &&
+  if (op_len > 0 && op_len % 16 == 0 && op_len <= (uint32_t)kReqTileMax &&
       ((uintptr_t)ops & 15u) == 0) {
     const size_t lds = (size_t)64 * (op_len / 4 + 1) * 4;
     hipLaunchKernelGGL(k_request_e_tiled, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st, seq,
@@ -3086,28 +2999,14 @@ hipError_t generator_xy(uint32_t* xy16, hipStream_t st) {
 // tot (G_l planes) and, below the top level, inv_tot (G_l planes).
 namespace {
 constexpr long kChain = 16, kMaxRoots = kTopMax;
-// Level 0 (the batch itself) may use longer chains (env MBFT_NINV_CHAIN0):
-// fewer, longer-lived waves beside the previous batch's verify kernel.
-long chain0() {
-  static const long c = [] {
-    const char* v = getenv("MBFT_NINV_CHAIN0");
-    return v && atol(v) > 0 ? atol(v) : kChain;
-  }();
-  return c;
-}
-long ninv_groups(long m, bool level0) {
-  const long c = level0 ? chain0() : kChain;
-  return (m + c - 1) / c;
-}
+long ninv_groups(long m) { return (m + kChain - 1) / kChain; }
 }  // namespace
 
 size_t ninv_workspace_words(long n) {
   size_t words = (size_t)NL * kTopMax;  // k_ninv_top's prefixes
   long m = n;
-  bool l0 = true;
   do {
-    const long G = ninv_groups(m, l0);
-    l0 = false;
+    const long G = ninv_groups(m);
     words += (size_t)NL * (m + 2 * G);
     m = G;
   } while (m > kMaxRoots);
@@ -3127,7 +3026,7 @@ hipError_t batch_inverse_s(const uint8_t* s, long n, uint32_t* ws, uint32_t* win
   do {
     Level L;
     L.m = m;
-    L.G = ninv_groups(m, nl == 0);
+    L.G = ninv_groups(m);
     L.pre = wp;  wp += (size_t)NL * L.m;
     L.tot = wp;  wp += (size_t)NL * L.G;
     L.itot = wp; wp += (size_t)NL * L.G;
@@ -3135,20 +3034,10 @@ hipError_t batch_inverse_s(const uint8_t* s, long n, uint32_t* ws, uint32_t* win
     m = L.G;
   } while (m > kMaxRoots && nl < 16);
   // up-sweeps: level 0 reads s directly, level l > 0 reads level l-1's totals
-  // level 0 with one chain per thread; env MBFT_NINV_CHAINS=2: two
-  // (k_ninv_up2 / k_ninv_down2) -- measured 1.4 % SLOWER in the pipelined
-  // C2 loop (the chain span 0.30 -> 0.355 ms, profiles/round4_chains_ab.txt)
-  static const bool two = [] {
-    const char* v = getenv("MBFT_NINV_CHAINS");
-    return v && atoi(v) == 2;
-  }();
   for (int l = 0; l < nl; l++) {
     const Level& L = lv[l];
     const dim3 grid((unsigned)((L.G + 255) / 256)), block(256);
-    if (l == 0 && two)
-      hipLaunchKernelGGL(k_ninv_up2, dim3((unsigned)(((L.G + 1) / 2 + 255) / 256)), block, 0, st, s, L.m, L.G,
-                         L.pre, L.tot);
-    else if (l == 0)
+    if (l == 0)
       hipLaunchKernelGGL(k_ninv_up<true>, grid, block, 0, st, nullptr, s, L.m, L.G, L.pre, L.tot);
     else
       hipLaunchKernelGGL(k_ninv_up<false>, grid, block, 0, st, lv[l - 1].tot, nullptr, L.m, L.G,
@@ -3164,10 +3053,7 @@ hipError_t batch_inverse_s(const uint8_t* s, long n, uint32_t* ws, uint32_t* win
   for (int l = nl - 1; l >= 0; l--) {
     const Level& L = lv[l];
     const dim3 grid((unsigned)((L.G + 255) / 256)), block(256);
-    if (l == 0 && two)
-      hipLaunchKernelGGL(k_ninv_down2, dim3((unsigned)(((L.G + 1) / 2 + 255) / 256)), block, 0, st, s, L.pre,
-                         L.m, L.G, L.itot, winv, zero_word);
-    else if (l == 0)
+    if (l == 0)
       hipLaunchKernelGGL(k_ninv_down<true>, grid, block, 0, st, nullptr, s, L.pre, L.m, L.G,
                          L.itot, winv, zero_word);
     else
@@ -3177,7 +3063,8 @@ hipError_t batch_inverse_s(const uint8_t* s, long n, uint32_t* ws, uint32_t* win
   return hipGetLastError();
 }
 
-// The one-launch form (k_ninv_local) for a batch on an idle GPU.
+// The one-launch forms: chains of PER per wave (k_ninv_local) or per
+// workgroup (k_ninv_block).
 template <int PER>
 hipError_t launch_ninv_local(const uint8_t* s, long n, uint32_t* winv, uint32_t* zero_word,
                              hipStream_t st, const uint32_t* ndev = nullptr) {
@@ -3196,28 +3083,11 @@ hipError_t launch_ninv_block(const uint8_t* s, long n, uint32_t* winv, uint32_t*
   return hipGetLastError();
 }
 
-// Env MBFT_NINV_PER: the chain length (per-block form: 2, 4, 8 default;
-// per-wave form k_ninv_local with MBFT_NINV_FORM=wave: 2, 4, 8, 16 default).
+// The s^-1 of a batch on an idle GPU: the per-workgroup form, chains of 8.
 hipError_t batch_inverse_s_local(const uint8_t* s, long n, uint32_t* winv, uint32_t* zero_word,
                                  hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  static const bool wave = [] {
-    const char* v = getenv("MBFT_NINV_FORM");
-    return v && strcmp(v, "wave") == 0;
-  }();
-  static const int per = [] {
-    const char* v = getenv("MBFT_NINV_PER");
-    return v ? atoi(v) : (wave ? 16 : 8);
-  }();
-  if (!wave) {
-    if (per == 2) return launch_ninv_block<2>(s, n, winv, zero_word, st);
-    if (per == 4) return launch_ninv_block<4>(s, n, winv, zero_word, st);
-    return launch_ninv_block<8>(s, n, winv, zero_word, st);
-  }
-  if (per == 2) return launch_ninv_local<2>(s, n, winv, zero_word, st, nullptr);
-  if (per == 8) return launch_ninv_local<8>(s, n, winv, zero_word, st, nullptr);
-  if (per == 16) return launch_ninv_local<16>(s, n, winv, zero_word, st, nullptr);
-  return launch_ninv_local<4>(s, n, winv, zero_word, st, nullptr);
+  return launch_ninv_block<8>(s, n, winv, zero_word, st);
 }
 
 // The s^-1 of a batch issued while earlier batches are in flight (the
@@ -3226,26 +3096,10 @@ hipError_t batch_inverse_s_local(const uint8_t* s, long n, uint32_t* winv, uint3
 // batch's verify waves wave by wave.  Same-box A/B in the C2 loop (3 caller
 // streams, tools/steady_ab.py, profiles/round6_ninv_forms.jsonl): 0.954 ms a
 // step against 0.969 (per-block form) and 1.048 (the level chain on the
-// high-priority stream, round 5's default).  Env MBFT_NINV_PIPE_FORM = block |
-// wave and MBFT_NINV_PIPE_PER override.
+// high-priority stream, round 5's default).
 hipError_t batch_inverse_s_pipelined(const uint8_t* s, long n, uint32_t* winv, uint32_t* zero_word,
                                      hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  static const bool block = [] {
-    const char* v = getenv("MBFT_NINV_PIPE_FORM");
-    return v && strcmp(v, "block") == 0;
-  }();
-  static const int per = [] {
-    const char* v = getenv("MBFT_NINV_PIPE_PER");
-    return v ? atoi(v) : (block ? 8 : 16);
-  }();
-  if (block) {
-    if (per == 4) return launch_ninv_block<4>(s, n, winv, zero_word, st);
-    return launch_ninv_block<8>(s, n, winv, zero_word, st);
-  }
-  if (per == 4) return launch_ninv_local<4>(s, n, winv, zero_word, st, nullptr);
-  if (per == 8) return launch_ninv_local<8>(s, n, winv, zero_word, st, nullptr);
-  if (per == 32) return launch_ninv_local<32>(s, n, winv, zero_word, st, nullptr);
   return launch_ninv_local<16>(s, n, winv, zero_word, st, nullptr);
 }
 
@@ -3271,10 +3125,7 @@ size_t verify_words(long n, bool pairs) {
 // k_verify_split's additions: lane-group parallel (default) or sequential
 // (env MBFT_SPLIT_WIDE=0)
 static bool split_wide() {
-  static const bool w = [] {
-    const char* v = getenv("MBFT_SPLIT_WIDE");
-    return !(v && atoi(v) == 0);
-  }();
+  static const bool w = env_on("MBFT_SPLIT_WIDE", true);
   return w;
 }
 
@@ -3308,14 +3159,10 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
   // the smallest batches: one item per 4-wave workgroup (k_verify_split);
   // split_max < 0: env MBFT_SPLIT_MAX, default 256 (at most one wave per
   // SIMD); 0 disables (mbft_set_small_batch_form)
-  static const long split_env = [] {
-    const char* v = getenv("MBFT_SPLIT_MAX");
-    return v ? atol(v) : 256L;
-  }();
+  static const long split_env = env_long("MBFT_SPLIT_MAX", 256L);
   if (split_max < 0) split_max = split_env;
   // The small batches' form past the split kernel's: small_form
-  // (mbft_set_small_batch_inverse;
-  // -1: env MBFT_PAIRS_PLANES, MBFT_QUADS, MBFT_QUADS_INLINE, default 2):
+  // (mbft_set_small_batch_inverse; -1: the default, 2):
   // 0 one item per lane pair inverting s per lane (a wave's ~38 us of
   // divsteps on the critical path); 1 the batched per-wave s^-1 into
   // planes_ws first, then the lane pairs (same box, one batch at a time,
@@ -3324,15 +3171,7 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
   // 768-4,096 items, profiles/round6_quads_ab.json); 2 the lane quads with
   // the s^-1 by each wave inside the kernel (no separate launch, no planes:
   // 76-77 us, profiles/round6_quads_inline_ab.json)
-  static const int pp_env = [] {
-    const char* v = getenv("MBFT_PAIRS_PLANES");
-    const char* q = getenv("MBFT_QUADS");
-    const char* qi = getenv("MBFT_QUADS_INLINE");
-    const int planes = v ? (atoi(v) != 0 ? 1 : 0) : 1;
-    if (!planes || (q && atoi(q) == 0)) return planes;
-    return qi && atoi(qi) == 0 ? 3 : 2;
-  }();
-  const int form = small_form < 0 ? pp_env : small_form;
+  const int form = small_form < 0 ? 2 : small_form;
   if (split_winv) {  // host s^-1 R planes (winv): the split kernel's, else unused
     // (the host stages u1, u2 after the 9 planes: 16 words an item, batch.cpp
     // host_winv_u)
@@ -3360,10 +3199,7 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
     hipError_t me = hipMemsetAsync(slowq + n, 0, 4, st);
     if (me != hipSuccess) return me;
   }
-  static const int bpc = [] {
-    const char* v = getenv("MBFT_VERIFY_BPC");
-    return v ? atoi(v) : 0;
-  }();
+  static const int bpc = (int)env_long("MBFT_VERIFY_BPC", 0);
   static const int ncu = [] {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess)
@@ -3409,29 +3245,12 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
   if (bpc > 0 && blocks > (long)bpc * ncu) blocks = (long)bpc * ncu;
   const dim3 grid((unsigned)blocks), block(256);
   A.sstride = (uint32_t)(blocks * 256);  // <= verify_words' 256-rounded n
-  // MBFT_VERIFY_WAVES=4 selects the 128-VGPR build (4 waves/SIMD, spills a
-  // little), =2 the 256-VGPR build (2 waves/SIMD: a 1M grid is exactly 8
-  // rounds of resident blocks, no partial last round); default 3 waves/SIMD
-  // (no spills).
-  static const int minw = [] {
-    const char* v = getenv("MBFT_VERIFY_WAVES");
-    const int w = v ? atoi(v) : 3;
-    return (w == 2 || w == 4) ? w : 3;
-  }();
-  if (minw == 3)
-    hipLaunchKernelGGL((k_verify<3>), grid, block, 0, st, A);
-  else if (minw == 2)
-    hipLaunchKernelGGL((k_verify<2>), grid, block, 0, st, A);
-  else
-    hipLaunchKernelGGL((k_verify<4>), grid, block, 0, st, A);
-  // the queued items: a grid of up to `sbpc` blocks per CU (env
-  // MBFT_SLOW_BPC, default 4 = one wave per SIMD) that exits at once when
-  // the queue is empty
-  static const int sbpc = [] {
-    const char* v = getenv("MBFT_SLOW_BPC");
-    return v && atoi(v) > 0 ? atoi(v) : 4;
-  }();
-  long sblocks = (n + 255) / 256 < (long)ncu * sbpc ? (n + 255) / 256 : (long)ncu * sbpc;
+  // MINW = 3 waves/SIMD (the trace summaries under profiles/ name k_verify<3>)
+  hipLaunchKernelGGL((k_verify<3>), grid, block, 0, st, A);
+  // the queued items: a grid of up to kSlowBpc blocks per CU (one wave per
+  // SIMD) that exits at once when the queue is empty
+  constexpr int kSlowBpc = 4;
+  long sblocks = (n + 255) / 256 < (long)ncu * kSlowBpc ? (n + 255) / 256 : (long)ncu * kSlowBpc;
   if (sblocks > blocks) sblocks = blocks;  // its threads index the same spill planes (A.sstride)
   if (winv) hipLaunchKernelGGL(k_verify_slow, dim3((unsigned)sblocks), dim3(256), 0, st, A);
   return hipGetLastError();

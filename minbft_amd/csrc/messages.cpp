@@ -583,7 +583,7 @@ int run_message_calls(mbft_ctx* c, const mbft_message* msgs, size_t n,
     for (size_t k = nc * t / T; k < nc * (t + 1) / T; k++)
       gst[k] = info[k].pre != 0xFF ? info[k].pre : hs[k];
   });
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   if (trace)
     fprintf(stderr, "[mbft calls] nc=%zu nop=%zu T=%d dedup_ops=%.3f host_prep=%.3f gpu_round_trip=%.3f "
             "statuses=%.3f ms\n", nc, nop, T,
@@ -784,7 +784,7 @@ int run_calls_small(mbft_ctx* c, mbft_ctx* g, const mbft_message* msgs, size_t n
   info.assign(nc, CallInfo());
   gst.assign(nc, 0);
   if (nc == 0) return MBFT_OK;
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   const auto ta = std::chrono::steady_clock::now();
   size_t cap = 16;
   while (cap < 2 * n) cap <<= 1;
@@ -1028,7 +1028,7 @@ extern "C" int mbft_validate_messages(mbft_ctx* c, const mbft_message* msgs, siz
                        [&](size_t i) { return msgs[i].stream; },
                        [&](uint32_t k) { return calls[k].role; });
   if (rc) return rc;
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   if (trace) {
     const auto t3 = std::chrono::steady_clock::now();
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

@@ -32,6 +32,7 @@
 #include "arena_dev.h"
 #include "authen_dev.h"
 #include "der_dev.h"
+#include "env.h"
 #include "msg_dev.h"
 #include "sha256_dev.h"
 
@@ -668,18 +669,15 @@ hipError_t msg_init(const MsgDevArgs& a, uint32_t* flags, uint32_t* bounds, hipS
   // (profiles/round6_kcopy_block_ab.json).
   const uint64_t ub = (up0 ? up0->bytes : 0) + (up1 ? up1->bytes : 0);
   static const uint64_t per_block = [] {
-    const char* v = getenv("MBFT_MSG_KCOPY_BLOCK");
-    const uint64_t x = v ? strtoull(v, nullptr, 10) : 65536u;
+    const uint64_t x = env_size("MBFT_MSG_KCOPY_BLOCK", 65536u);
     return x >= 256u ? x : (uint64_t)65536u;
   }();
   long ublocks = (long)((ub + per_block - 1) / per_block);
   if (ublocks > blocks) blocks = ublocks;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  static const long umax = [] {  // env MBFT_MSG_KCOPY_UBLOCKS: at most this many workgroups upload (A/B)
-    const char* v = getenv("MBFT_MSG_KCOPY_UBLOCKS");
-    return v ? atol(v) : 2048L;
-  }();
+  // env MBFT_MSG_KCOPY_UBLOCKS: at most this many workgroups upload (A/B)
+  static const long umax = env_long("MBFT_MSG_KCOPY_UBLOCKS", 2048L);
   ublocks = blocks < umax ? blocks : (umax > 0 ? umax : 1);
   const MsgUpload none{nullptr, nullptr, 0, 0};
   hipLaunchKernelGGL(k_msg_init, dim3((unsigned)blocks), dim3(256), 0, st, flags, bounds, a.tkeys, a.treps,

@@ -298,10 +298,7 @@ int validate_flat_device_impl(mbft_ctx* c, mbft_ctx* g, const mbft_msg_rec* recs
   // copies: each hand-off between the copy engine and the compute queue
   // cost ~8-11 us (init -> copy -> copy -> k_msg_cands: ~29 us of a
   // 1,024-message pass, profiles/round6_midsize_timeline_*.json).
-  static const size_t kcopy_max = [] {
-    const char* v = getenv("MBFT_MSG_KCOPY_MAX");
-    return v ? (size_t)strtoull(v, nullptr, 10) : (size_t)4 << 20;
-  }();
+  static const size_t kcopy_max = mbft::env_size("MBFT_MSG_KCOPY_MAX", (size_t)4 << 20);
   const size_t rec_bytes = sizeof(mbft_msg_rec) * n;
   const bool kcopy = K == 1 && rec_bytes + up <= kcopy_max && (((uintptr_t)recs | (uintptr_t)(bytes + abase)) & 15u) == 0;
   MsgProf prof(g);
@@ -326,11 +323,8 @@ int validate_flat_device_impl(mbft_ctx* c, mbft_ctx* g, const mbft_msg_rec* recs
   }
   if (cs != st) HIPCHK(g, hipMemsetAsync(tail6, 0, 24, cs));
   if (up && !kcopy) HIPCHK(g, hipMemcpyAsync(g->m_bytes.p, bytes + abase, up, hipMemcpyHostToDevice, cs));
-  static const int split_at = [] {  // env MBFT_MSG_VERIFY_SPLIT: the first stage's last chunk (-1: one stage)
-    const char* v = getenv("MBFT_MSG_VERIFY_SPLIT");
-    return v ? atoi(v) : 3;
-  }();
-  const int S = K > 1 && split_at >= 0 && split_at < K - 1 ? split_at : -1;
+  constexpr int kSplitAt = 3;  // the first verify stage's last chunk
+  const int S = K > 1 && kSplitAt < K - 1 ? kSplitAt : -1;
   // A small check (one chunk, <= kOneWaitMsgs messages) waits on the host
   // once: the unique-call count stays on the device, k_msg_calls and the
   // small-batch verifier (pairs / split: no s^-1 chain sized on the host) run
@@ -339,25 +333,14 @@ int validate_flat_device_impl(mbft_ctx* c, mbft_ctx* g, const mbft_msg_rec* recs
   // would run the small-batch verifier too (3n <= 4,096 calls): for a
   // 4,096-message stream batch (12,288 calls) the per-lane s^-1 costs more
   // than the wait saves (0.56 vs 0.49 ms p50 alone, and half the rate with 4
-  // lanes at once; profiles/round4_msg_pass_ab.txt).  Env MBFT_MSG_ONE_WAIT=0:
-  // the two-wait form always.
-  static const bool one_wait_env = [] {
-    const char* v = getenv("MBFT_MSG_ONE_WAIT");
-    return !(v && atoi(v) == 0);
-  }();
-  static const size_t kOneWaitMsgs = [] {  // env MBFT_MSG_ONE_WAIT_MAX (messages)
-    const char* v = getenv("MBFT_MSG_ONE_WAIT_MAX");
-    return v ? (size_t)strtoull(v, nullptr, 10) : (size_t)(4096 / 3);
-  }();
-  const bool one_wait = one_wait_env && chk && K == 1 && n <= kOneWaitMsgs;
+  // lanes at once; profiles/round4_msg_pass_ab.txt).  Env
+  // MBFT_MSG_ONE_WAIT_MAX (messages; 0: the two-wait form always).
+  static const size_t kOneWaitMsgs = mbft::env_size("MBFT_MSG_ONE_WAIT_MAX", (size_t)(4096 / 3));
+  const bool one_wait = chk && K == 1 && n <= kOneWaitMsgs;
   // A one-chunk pass of up to 1,365 messages numbers its calls in one
   // single-workgroup launch (msg_number_one) instead of the hipcub scan,
-  // k_chunk_base and k_call_list; env MBFT_MSG_NUMBER_ONE=0: never.
-  static const bool number_one_env = [] {
-    const char* v = getenv("MBFT_MSG_NUMBER_ONE");
-    return !(v && atoi(v) == 0);
-  }();
-  const bool listed = number_one_env && K == 1 && 3 * (long)n <= mbft_launch::kNumberOneMax;
+  // k_chunk_base and k_call_list.
+  const bool listed = K == 1 && 3 * (long)n <= mbft_launch::kNumberOneMax;
   size_t tmp_bytes = 0;
   HIPCHK(g, mbft_launch::msg_scan(a, 0, 0, (long)((n + K - 1) / K + 1), nullptr, &tmp_bytes, st));
   HIPCHK(g, g->m_scan.ensure(tmp_bytes + 16));
@@ -511,7 +494,7 @@ int validate_flat_device_impl(mbft_ctx* c, mbft_ctx* g, const mbft_msg_rec* recs
         [&](size_t i) { return recs[i].stream; },
         [&](uint32_t k) { return (uint32_t)role_bytes[sizeof(CallInfo) * k]; });
   }
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   if (trace)
     fprintf(stderr,
             "[mbft validate flat dev] n=%zu calls=%zu bytes=%zu up+cands+dedup=%.3f "
@@ -606,7 +589,7 @@ int check_small(mbft_ctx* c, mbft_ctx* g, const mbft_message* msgs, size_t n, ui
                                       calls->role);
   if (rc) return rc;
   chk->calls = std::move(calls);
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   if (trace)
     fprintf(stderr, "[mbft check small] n=%zu calls=%zu %.3f ms\n", n, chk->calls->gst.size(), ms_since(t0));
   return MBFT_OK;
@@ -996,7 +979,7 @@ void check_merged(mbft_ctx* c, mbft_ctx* g, const std::vector<mbft_check_req*>& 
     b->calls = merged.calls;
     rs[j]->out = b;
   }
-  static const bool trace = getenv("MBFT_STAGE_TRACE") != nullptr;
+  static const bool trace = mbft::env_set("MBFT_STAGE_TRACE");
   if (trace)
     fprintf(stderr, "[mbft check pass] batches=%zu messages=%zu bytes=%zu stage=%.3f device=%.3f split=%.3f ms\n",
             R, N, NB, t_stage, t_dev, ms_since(t0) - t_stage - t_dev);
@@ -1035,8 +1018,8 @@ int check_coalesced(mbft_ctx* c, mbft_check_req& me) {
   // 24.4 M messages/s on 2 lanes against 20.2 M on 4,
   // profiles/round4_msg_pass_ab.txt).  The queue fills meanwhile.
   static const int max_passes = [] {
-    const char* v = getenv("MBFT_CHECK_PASSES");
-    return v && atoi(v) > 0 ? atoi(v) : 2;
+    const int v = (int)mbft::env_long("MBFT_CHECK_PASSES", 0);
+    return v > 0 ? v : 2;
   }();
   co.cv.wait(lk, [&] { return co.running < max_passes; });
   co.running++;

@@ -29,7 +29,6 @@
 #include <time.h>
 
 #include <chrono>
-#include <map>
 
 #include "host_internal.h"
 
@@ -46,10 +45,7 @@ double now_ms() {
       .count();
 }
 
-uint32_t env_u32(const char* name, uint32_t dflt) {
-  const char* v = getenv(name);
-  return v ? (uint32_t)strtoul(v, nullptr, 10) : dflt;
-}
+using mbft::env_u32;
 
 }  // namespace
 
@@ -59,7 +55,6 @@ struct Resident {
   uint8_t* host = nullptr;  // SrvCtl, then nslots SrvSlot (host view)
   uint8_t* dev = nullptr;   // the same, device view
   hipStream_t stream = nullptr;
-  bool cu_mask = false;     // the stream was created with a CU mask (its own hardware queue)
   bool low_prio = false;    // the stream has the lowest priority (its own hardware queue)
   DevBuf d_st, d_exit, d_claim;
   int servers = 0;          // workgroups of the server pool (k_verify_server's grid)
@@ -190,75 +185,24 @@ int acquire_slot(Resident& R) {
 // shared queue a batch would wait up to the kernel's 20 ms lifetime).  It is
 // non-blocking, so null-stream work of the application (a synchronous
 // hipMemcpy, torch's default stream) does not wait for the live generation
-// either -- round 5's CU-masked stream did both (hipExtStreamCreateWithCUMask
-// takes no flags: a blocking stream) and, never destroyed, was still
+// either.  (Round 5's CU-masked stream did both -- hipExtStreamCreateWithCUMask
+// takes no flags: a blocking stream -- and, never destroyed, was still
 // registered when rocprofv3's destructors ran after the HSA runtime's
-// shutdown, which faulted at exit.  MBFT_RESIDENT_CUMASK=1:
-// the round-5 CU-masked stream (one per device, lent to one context at a
-// time, destroyed at exit).
-std::mutex g_cu_mu;
-std::map<int, std::pair<hipStream_t, bool>> g_cu_streams;  // device -> (stream, lent)
-
-void destroy_cu_streams_at_exit() {
-  std::lock_guard<std::mutex> l(g_cu_mu);
-  for (auto& kv : g_cu_streams) {
-    if (!kv.second.first || kv.second.second) continue;  // lent: its context is still open
-    if (hipSetDevice(kv.first) == hipSuccess) {
-      (void)hipStreamSynchronize(kv.second.first);
-      (void)hipStreamDestroy(kv.second.first);
-    }
-    kv.second.first = nullptr;
-  }
-  (void)hipGetLastError();
-}
-
-hipError_t create_stream(mbft_ctx* c, Resident& R) {
-  if (env_u32("MBFT_RESIDENT_CUMASK", 0) != 0) {
-    std::lock_guard<std::mutex> l(g_cu_mu);
-    static const bool registered = [] {
-      return atexit(destroy_cu_streams_at_exit) == 0 || true;
-    }();
-    (void)registered;
-    auto it = g_cu_streams.find(c->device);
-    if (it == g_cu_streams.end()) {
-      int cus = 0;
-      hipStream_t st = nullptr;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess &&
-          cus > 0) {
-        std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0xFFFFFFFFu);
-        if (cus % 32) mask.back() = (1u << (cus % 32)) - 1u;
-        if (hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
-          (void)hipGetLastError();
-          st = nullptr;
-        }
-      }
-      it = g_cu_streams.emplace(c->device, std::make_pair(st, false)).first;
-    }
-    if (it->second.first && !it->second.second) {
-      it->second.second = true;
-      R.stream = it->second.first;
-      R.cu_mask = true;
-      return hipSuccess;
-    }
-  }
+// shutdown, which faulted at exit; DESIGN.md §4.4.  That form was removed.)
+hipError_t create_stream(Resident& R) {
   int lo = 0, hi = 0;
   if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = 0;
   R.low_prio = lo != hi;
   return hipStreamCreateWithPriority(&R.stream, hipStreamNonBlocking, lo);
 }
 
-void release_stream(int device, Resident& R) {
+void release_stream(Resident& R) {
   if (!R.stream) return;
-  if (R.cu_mask) {
-    std::lock_guard<std::mutex> l(g_cu_mu);
-    g_cu_streams[device].second = false;
-  } else {
-    (void)hipStreamDestroy(R.stream);
-  }
+  (void)hipStreamDestroy(R.stream);
   R.stream = nullptr;
 }
 
-void free_resident(int device, Resident* R) {
+void free_resident(Resident* R) {
   if (!R) return;
   unregister_resident(R);
   {
@@ -269,7 +213,7 @@ void free_resident(int device, Resident* R) {
   R->d_exit.release();
   R->d_claim.release();
   if (R->host) (void)hipHostFree(R->host);
-  release_stream(device, *R);
+  release_stream(*R);
   delete R;
 }
 
@@ -298,7 +242,7 @@ void resident_destroy(mbft_ctx* c) {
   c->res_on.store(false);
   if (R) {
     (void)hipSetDevice(c->device);
-    free_resident(c->device, R);
+    free_resident(R);
   }
 }
 
@@ -726,8 +670,7 @@ int mbft_set_resident(mbft_ctx* c, int slots) {
   R->life_ms = std::min<uint32_t>(R->life_ms, 10000u);
   R->idle_us = std::min<uint32_t>(R->idle_us, R->life_ms * 1000u);
   {
-    const char* f = getenv("MBFT_RESIDENT_FORM");
-    R->two = !(f && strcmp(f, "one") == 0);
+    R->two = !mbft::env_is("MBFT_RESIDENT_FORM", "one");
     R->host_u = env_u32("MBFT_RESIDENT_HOST_U", 1) != 0;
     R->host_join_max = env_u32("MBFT_RESIDENT_HOST_JOIN_MAX", 4);
     R->sleep = env_u32("MBFT_RESIDENT_SLEEP", 1) != 0;
@@ -741,7 +684,7 @@ int mbft_set_resident(mbft_ctx* c, int slots) {
   void* h = nullptr;
   void* d = nullptr;
   auto bail = [&](const char* what) {
-    free_resident(c->device, R);
+    free_resident(R);
     return fail(c, MBFT_ERR_HIP, std::string("resident verifier: ") + what);
   };
   if (host_malloc_near(&h, bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
@@ -752,7 +695,7 @@ int mbft_set_resident(mbft_ctx* c, int slots) {
   memset(h, 0, bytes);
   if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess || !d) return bail("device view of the mailbox");
   R->dev = static_cast<uint8_t*>(d);
-  if (create_stream(c, *R) != hipSuccess) return bail("stream");
+  if (create_stream(*R) != hipSuccess) return bail("stream");
   // device scratch, initialized on the server's own stream (a null-stream
   // memset would wait for every blocking stream of the device)
   {
@@ -805,7 +748,7 @@ int mbft_resident_stats(mbft_ctx* c, double out[6]) {
   out[2] = (double)R->launches.load();
   out[3] = (double)R->fallbacks.load();
   out[4] = (double)R->stream_relaunches.load();
-  out[5] = R->cu_mask || R->low_prio ? 1.0 : 0.0;
+  out[5] = R->low_prio ? 1.0 : 0.0;
   return MBFT_OK;
 }
 

@@ -27,8 +27,7 @@ namespace {
 // Env MBFT_HOST_SHA=portable forces the portable compression (A/B only).
 int default_form() {
   static const int f = [] {
-    const char* v = getenv("MBFT_HOST_SHA");
-    if (v && strcmp(v, "portable") == 0) return 0;
+    if (mbft::env_is("MBFT_HOST_SHA", "portable")) return 0;
     return cpu_has_shani() ? 1 : 0;
   }();
   return f;

@@ -2,9 +2,8 @@
 """In-kernel clock of k_verify (a -DMBFT_CLOCK_STAMP build through
 MBFT_LIB_PATH): Δs_memtime ÷ Δs_memrealtime × 100 MHz summed over every
 workgroup, (a) over isolated 1M launches one at a time after idle, (b) over
-the pipelined C2 loop (3 streams) after >= 2 s of back-to-back steps, (c) the
-same loop with the s^-1 stage reused (MBFT_DIAG_REUSE_WINV is read by the
-library at start: run the script twice for it).  One JSON line."""
+the pipelined C2 loop (3 streams) after >= 2 s of back-to-back steps.  One
+JSON line."""
 import ctypes
 import json
 import os
@@ -27,7 +26,7 @@ def main():
         fn(out, 1 if reset else 0)
         return {"ghz": out[0] / out[1] / 10.0 if out[1] else None, "blocks": int(out[2])}
 
-    res = {"reuse_winv": os.environ.get("MBFT_DIAG_REUSE_WINV")}
+    res = {}
     try:
         read()
         iso = []

@@ -1,9 +1,9 @@
 """Latency of one 1M C2 batch on an idle GPU (mbft_verify_prehashed_device,
 host-synchronized, p50 of 40 after 5 warm-ups): the one-launch s^-1 form for
-idle batches (env MBFT_NINV_FORM / MBFT_NINV_PER) + k_verify + the exact-path
-launch -- bench.py's p50_batch_latency_device_ms.  Prints one JSON object.
+idle batches (k_ninv_block) + k_verify + the exact-path launch -- bench.py's
+p50_batch_latency_device_ms.  Prints one JSON object.
 
-    MBFT_NINV_FORM=wave MBFT_NINV_PER=16 python tools/idle_batch_probe.py
+    python tools/idle_batch_probe.py
 """
 import json
 import os
@@ -33,8 +33,7 @@ def main():
         ok = int((c.d_sts[0] == 0).sum().item())
     finally:
         c.close()
-    print(json.dumps({"form": os.environ.get("MBFT_NINV_FORM", "block"), "per": os.environ.get("MBFT_NINV_PER", "default"),
-                      "p50_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4),
+    print(json.dumps({"p50_ms": round(float(np.median(ts)) * 1e3, 4), "min_ms": round(min(ts) * 1e3, 4),
                       "accepted": ok, "items": c.B}))
     if ok != c.B:
         raise SystemExit("not all accepted")

@@ -1,11 +1,10 @@
 """Latency of small device batches through mbft_verify_prehashed_device (one
-batch at a time, host-synchronized), under whatever small-batch form the
-environment selects (kernels.hip verify(): MBFT_SPLIT_MAX, MBFT_PAIRS_PLANES,
-MBFT_QUADS, MBFT_QUADS_INLINE; round 6 also MBFT_SPLIT_PLANES_MAX, since
-dropped).  Every status checked (all valid, then 1 in 7 tampered).  Prints
-one JSON object.
+batch at a time, host-synchronized), under the small-batch form SMALL_FORM
+selects (mbft_set_small_batch_inverse's modes 0..3; unset: the default) and
+MBFT_SPLIT_MAX.  Every status checked (all valid, then 1 in 7 tampered).
+Prints one JSON object.
 
-    MBFT_QUADS=0 python tools/small_batch_probe.py   # lane pairs on the planes
+    SMALL_FORM=1 python tools/small_batch_probe.py   # lane pairs on the planes
     python tools/small_batch_probe.py                # the default (lane quads)
 """
 import json
@@ -28,8 +27,11 @@ def main():
     c = C2(B=max(sizes), streams=1)
     torch = c.torch
     st = c.streams[0]
+    form = os.environ.get("SMALL_FORM")
+    if form is not None:
+        c.auth.set_small_batch_inverse(int(form))
     env = {k: v for k, v in os.environ.items() if k.startswith("MBFT_")}
-    out = {"env": env, "sizes": {}}
+    out = {"env": env, "small_form": form, "sizes": {}}
     bad_e = c.d_e.clone()
     bad_e[::7, 5] ^= 1
     try:

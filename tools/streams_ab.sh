@@ -1,6 +1,5 @@
 #!/bin/bash
-# Batches in flight (--streams) A/B on one box, optionally with the
-# diagnostic s^-1 reuse (DIAG=1: MBFT_DIAG_REUSE_WINV, the s^-1 stage's share).
+# Batches in flight (--streams) A/B on one box.
 # Output under $OUT_DIR (default bench_out/).
 set -o pipefail
 O=${OUT_DIR:-bench_out}
