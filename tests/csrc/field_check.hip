@@ -18,12 +18,12 @@ using namespace mbft;
 enum Op : uint32_t {
   OP_MUL = 0, OP_SQR = 1, OP_SUB = 2, OP_NEG = 3, OP_ADD = 4, OP_MUL2 = 5,
   OP_CANON = 6, OP_MULSMALL8 = 7, OP_MADD = 8, OP_DBL = 9, OP_SUB2X = 10,
-  OP_MULADD_P5B = 11, OP_MULADD_P2B = 12, OP_SUB5 = 13,
+  OP_MULADD_P5B = 11, OP_MULADD_P2B = 12, OP_SUB5 = 13, OP_FE_INV = 14,
   OP_CHUD_P = 16, OP_CHUD_N = 17, OP_AFF_CHUD_P = 18, OP_AFF_CHUD_N = 19,
   OP_CHUD_LAZY_P = 20, OP_CHUD_LAZY_N = 21, OP_CHUD_LAST_P = 22, OP_CHUD_LAST_N = 23,
   OP_NORM_LAZY = 24,
   OP_FN_MUL = 32, OP_FN_CANON = 33, OP_FN_CSUB1 = 34, OP_FN_TO_MONT = 35, OP_FN_FROM_MONT = 36,
-  OP_SCALARS = 37, OP_X_MATCHES = 38
+  OP_SCALARS = 37, OP_X_MATCHES = 38, OP_FN_INV = 39
 };
 
 // in: per case 6 field elements (9 limbs each): a, b, c, d, e, f
@@ -36,6 +36,7 @@ enum Op : uint32_t {
 // CHUD_LAST_P / _N: ec_madd_chud<LAZY, LAST> (X and ZZ only; Y, ZZZ = inputs)
 // NORM_LAZY: fe_norm_lazy(a)
 // DBL:  (X, Y, Z) = (a, b, c)
+// FE_INV: fe_inv(a); FN_INV: fn_inv(a) (the signer's fixed-exponent inversions, Montgomery in and out)
 // FN_MUL: fn_mul(a, b); FN_CANON / FN_CSUB1 / FN_TO_MONT / FN_FROM_MONT: of a
 // SCALARS: scalars(U1, U2, e = a, r = b, w = c); U1 -> out 0, U2 -> out 1 (8 words each)
 // X_MATCHES: x_matches_r(X = a, ZZ = b, rw = the first 8 words of c) -> out 0, word 0
@@ -112,6 +113,8 @@ __global__ void k_field(const uint32_t* op, const uint32_t* in, uint32_t* out, i
       r0 = a.X; r1 = a.Y; r2 = a.Z;
       break;
     }
+    case OP_FE_INV: fe_inv(r0, v[0]); break;
+    case OP_FN_INV: fn_inv(r0, v[0]); break;
     case OP_FN_MUL: fn_mul(r0, v[0], v[1]); break;
     case OP_FN_CANON: r0 = v[0]; fn_canon(r0); break;
     case OP_FN_CSUB1: r0 = v[0]; fn_csub(r0, 1); break;

@@ -160,15 +160,24 @@ def test_group_ops(harness):
     rng = random.Random(0x6A0)
     pts = [o.scalar_mult(rng.randrange(1, o.N), o.G) for _ in range(48)]
     cases, want = [], []
+    pushed = [0, 0]   # dbl, madd cases at the bounds
     for i in range(3000):
         p1, p2 = pts[rng.randrange(48)], pts[rng.randrange(48)]
         if p1[0] == p2[0]:
             continue
         z = rng.randrange(1, P)
         X, Y, Z = p1[0] * z * z % P, p1[1] * z * z * z % P, z
-        # Montgomery form, sometimes a non-canonical representative < 2^257
+        # Montgomery form, sometimes a non-canonical representative < 2^257,
+        # and every third case representatives up to ec_madd's own output
+        # bounds (X < 2^257 + 2^234, Y and Z < 2^258): the signer's comb feeds
+        # ec_madd its outputs up to 64 times
         m = [x * R % P for x in (X, Y, Z)]
-        m = [x + P if rng.randrange(4) == 0 else x for x in m]
+        if i % 3 == 0:
+            m = [push_up(x, P, lim, rng, pick=0 if i % 4 < 2 else None)
+                 for x, lim in zip(m, (SUB2X_OUT, 1 << 258, 1 << 258))]
+            pushed[i % 2] += 1
+        else:
+            m = [x + P if rng.randrange(4) == 0 else x for x in m]
         x2, y2 = p2[0] * R % P, p2[1] * R % P
         if i % 2:
             cases.append(("madd", m + [x2, y2]))
@@ -176,6 +185,7 @@ def test_group_ops(harness):
         else:
             cases.append(("dbl", m))
             want.append(o.point_add(p1, p1))
+    assert min(pushed) > 400
     res = run(harness, cases)
     bad = 0
     for (op, _), w, (X, Y, Z, _) in zip(cases, want, res):

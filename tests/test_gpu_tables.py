@@ -21,29 +21,13 @@ import random
 import numpy as np
 import pytest
 
+from comb_layout import entries, entry_bytes, last_bits, steps, window_bases, window_entries
 from oracle import p256 as o
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R = 1 << 261
 RUN = 32  # k_table_fill's run length (kFillRun)
-
-
-def steps(W):
-    return -(-256 // W)
-
-
-def last_bits(W):
-    return 256 - (steps(W) - 1) * W
-
-
-def entries(W):
-    return ((steps(W) - 1) << (W - 1)) + (1 << last_bits(W))
-
-
-def window_entries(W, win):
-    return 1 << (last_bits(W) if win == steps(W) - 1 else W - 1)
 
 
 @pytest.fixture(scope="module")
@@ -75,20 +59,6 @@ def xy_words(pts):
                          dtype=np.uint32).copy()
 
 
-def entry_bytes(pt):
-    return (pt[0] * R % o.P).to_bytes(32, "little") + (pt[1] * R % o.P).to_bytes(32, "little")
-
-
-def window_bases(p, W):
-    """2^(W win) P for every window."""
-    out, b = [], p
-    for _ in range(steps(W)):
-        out.append(b)
-        for _ in range(W):
-            b = o.point_add(b, b)
-    return out
-
-
 def test_table_geometry(harness):
     """table_entries / table_steps / table_words against the formula for every
     window the library accepts: a table allocated one entry short puts the
@@ -103,11 +73,12 @@ def test_table_geometry(harness):
         assert harness.table_check_words(W) == 16 * want
 
 
-@pytest.mark.parametrize("W", [4, 5, 7, 8, 11])
+@pytest.mark.parametrize("W", [4, 5, 6, 7, 8, 11])
 def test_tables_exhaustive(harness, W):
     """Every entry of two points' tables (G and a random key) at the small
     windows: W = 4 (8-entry windows: runs shorter than 32), 5 (a last window
-    of 2 entries), 7, 8, 11 (a last window of 8).  Catches a wrong run
+    of 2 entries), 6 (the signer's largest: 42 windows of 32 entries and a
+    last window of 16), 7, 8, 11 (a last window of 8).  Catches a wrong run
     geometry (run length, runs per window, the last window's own geometry),
     a wrong first multiple of a run, the doubling at d = 2, and a Z-ratio
     walked back one step off."""

@@ -178,6 +178,29 @@ def test_identity(lib):
             a.close()
 
 
+@pytest.mark.parametrize("w", [4, 5, 6])
+def test_identity_structured_keys(lib, w):
+    """The identity d G (k_sign_pubkey: sign_comb over the table the product
+    itself built) for the keys at which the comb's selects change state
+    (comb_layout.structured_scalars: a long stay at infinity, carry chains,
+    zero runs, the tie digit, the top window alone and its last entry), one
+    context per signer window, a fresh epoch per key."""
+    from comb_layout import structured_scalars
+    from test_gpu_field import golden_module
+    mg = golden_module()
+    keys = structured_scalars(w, mg.scalar_edge_values(random.Random(0x45444745)))
+    a = _new(lib, d=None, window=w)
+    try:
+        bad = []
+        for i, (name, d) in enumerate(keys):
+            a.usig_init(_dbytes(d), i)
+            if a.usig_id() != i.to_bytes(8, "big") + o.pkix_encode(o.pubkey(d)):
+                bad.append(name)
+        assert not bad, (len(bad), bad[:10])
+    finally:
+        a.close()
+
+
 def test_round_trip_verify_batch(lib, expected):
     """The UIs, in counter order, pass the verifier of a context that knows
     only the public key; the epoch is captured from counter 1."""
