@@ -85,6 +85,14 @@ type Config struct {
 	// Windows in bits (4..29).  Zero: sized from the HBM budget by
 	// DefaultWindows (include/minbft_gpu.h, mbft_plan_windows).
 	GeneratorWindow, ReplicaWindow, USIGWindow, ClientWindow int
+	// TableFreeClients registers client keys -- those given to New and those
+	// registered late from KeyStore -- with NO comb table (key window 0,
+	// MBFT_WINDOW_NONE): 64 bytes of HBM per key and no table build at
+	// registration, verified by a double-and-add ladder that costs many
+	// times a tabled verify per signature.  For open or very large client
+	// sets (INTEGRATION.md); ClientWindow is ignored.  A flag, since the
+	// zero value of the window fields means "default".
+	TableFreeClients bool
 	// Private keys of the ECDSA roles this node signs as (CPU signing with
 	// the reference scheme, crypto.go:63-76), used when Generator is nil.
 	PrivateKeys map[api.AuthenticationRole]*ecdsa.PrivateKey
@@ -314,17 +322,26 @@ type Windows struct {
 
 // DefaultWindows sizes the comb tables from the device's HBM and the key
 // counts (mbft_plan_windows, include/minbft_gpu.h); explicit Config windows
-// win.
+// win.  With Config.TableFreeClients the clients take no table memory (the
+// plan is made for none) and their window is 0.
 func DefaultWindows(nkeys map[api.AuthenticationRole]int, cfg Config) Windows {
 	var g, r, u, c C.int
+	nclients := nkeys[api.ClientAuthen]
+	if cfg.TableFreeClients {
+		nclients = 0
+	}
 	C.mbft_plan_windows(C.int(firstDevice(cfg)), C.size_t(nkeys[api.ReplicaAuthen]),
-		C.size_t(nkeys[api.USIGAuthen]), C.size_t(nkeys[api.ClientAuthen]), &g, &r, &u, &c)
-	return Windows{
+		C.size_t(nkeys[api.USIGAuthen]), C.size_t(nclients), &g, &r, &u, &c)
+	w := Windows{
 		Generator: orDefault(cfg.GeneratorWindow, int(g)),
 		Replica:   orDefault(cfg.ReplicaWindow, int(r)),
 		USIG:      orDefault(cfg.USIGWindow, int(u)),
 		Client:    orDefault(cfg.ClientWindow, int(c)),
 	}
+	if cfg.TableFreeClients {
+		w.Client = int(C.MBFT_WINDOW_NONE)
+	}
+	return w
 }
 
 func firstDevice(cfg Config) int {

@@ -178,7 +178,20 @@ int mbft_key_slot(const mbft_ctx* ctx, uint32_t role, uint32_t id);
  * generator table (258 GiB of 288), a 33-replica set at W = 24, a very
  * large client set at W = 8.  mbft_set_generator_window rebuilds the shared
  * generator table (default 16); it waits for in-flight work.
- * Both accept 4 <= W <= 29; MBFT_ERR_NOMEM if the table does not fit. */
+ * Both accept 4 <= W <= 29; MBFT_ERR_NOMEM if the table does not fit.
+ *
+ * mbft_set_key_window also accepts MBFT_WINDOW_NONE (0): keys registered
+ * after the call are TABLE-FREE.  Such a key costs 64 bytes of HBM (its point,
+ * in pooled blocks) and registers at the price of the on-curve check: no
+ * table build.  A signature under it is verified by a double-and-add ladder
+ * over the point instead of a comb -- about 2,900 field reductions an item
+ * against about 170 at W = 29, so far slower per item, but for any number of
+ * keys and from the moment a key is first seen.  Meant for open or very
+ * large client sets; every verify entry point serves such keys, and keys of
+ * every window, 0 included, live side by side in one context.  The generator
+ * always has a table: mbft_set_generator_window(ctx, 0) is MBFT_ERR_ARG, as
+ * are the windows 1..3 for both.  mbft_get_windows reports 0 while it is set. */
+#define MBFT_WINDOW_NONE 0
 int mbft_set_key_window(mbft_ctx* ctx, int wbits);
 int mbft_set_generator_window(mbft_ctx* ctx, int wbits);
 int mbft_get_windows(const mbft_ctx* ctx, int* g_wbits, int* q_wbits);

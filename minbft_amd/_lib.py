@@ -42,6 +42,9 @@ ROLE_REPLICA = 1
 ROLE_USIG = 2
 ROLE_CLIENT = 3
 
+#: key window of table-free keys (MBFT_WINDOW_NONE)
+WINDOW_NONE = 0
+
 #: bytes per tag slot of the batch signer (MBFT_TAG_SLOT)
 TAG_SLOT = 72
 #: bytes per UI slot of the software USIG (MBFT_UI_SLOT) and of its identity

@@ -172,7 +172,9 @@ class Authenticator:
 
     def set_key_window(self, wbits: int):
         """Comb window (4..29 bits, default 16) for keys registered after the
-        call; include/minbft_gpu.h lists the HBM cost per window."""
+        call; include/minbft_gpu.h lists the HBM cost per window.  0
+        (``WINDOW_NONE``): table-free keys -- 64 bytes each, no table build,
+        verified by a double-and-add ladder (open or very large client sets)."""
         self._check(self.lib.mbft_set_key_window(self.ctx, wbits), "set_key_window")
 
     def set_generator_window(self, wbits: int):

@@ -289,7 +289,41 @@ int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t*
         vslots.push_back((uint32_t)(base + j));
       }
     }
-    if (!vslots.empty()) {
+    if (!vslots.empty() && c->q_wbits == mbft_launch::kWindowNone) {
+      // table-free keys: each valid point as ONE comb entry, nothing else
+      const size_t cnt = vslots.size();
+      uint32_t* dst = nullptr;
+      if (cnt <= c->tfree_left) {
+        dst = c->tfree_chunk;
+      } else {
+        // a block of its own for a large call, else a fresh chunk (what is
+        // left of the old one stays unused)
+        const size_t ents = cnt >= mbft_ctx::kTfreeChunk / 4 ? cnt : mbft_ctx::kTfreeChunk;
+        hipError_t he = table_block(c, ents * 64, &dst);
+        if (he != hipSuccess) {
+          (void)hipGetLastError();
+          return fail(c, MBFT_ERR_NOMEM, "table-free keys: out of device memory");
+        }
+        if (ents != cnt) {
+          c->tfree_chunk = dst;
+          c->tfree_left = ents;
+        }
+      }
+      if (dst == c->tfree_chunk) {
+        c->tfree_chunk += 16 * cnt;
+        c->tfree_left -= cnt;
+      }
+      HIPCHK(c, c->xy.ensure(64 * cnt));
+      HIPCHK(c, hipMemcpyAsync(c->xy.p, vwords.data(), 64 * cnt, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, mbft_launch::point_entries(c->xy.as<uint32_t>(), (int)cnt, dst, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (size_t j = 0; j < cnt; j++) {
+        mbft::KeyDesc& kd = c->keydesc[vslots[j]];
+        kd.tab = dst + 16 * j;
+        kd.valid = 1;
+      }
+      c->tfree_keys += cnt;
+    } else if (!vslots.empty()) {
       const int w = c->q_wbits;
       const size_t cnt = vslots.size();
       const size_t tw = mbft_launch::table_words(w);
@@ -363,7 +397,7 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
                                   (long)n, d_status, c->slowq[k].as<uint32_t>(), st, host_status,
                                   queue_zeroed, tb->split_max, /*split_winv=*/d_winv != nullptr,
                                   d_count, /*planes_ws=*/d_winv ? nullptr : c->winv[k].as<uint32_t>(),
-                                  tb->small_inv));
+                                  tb->small_inv, /*table_free=*/tb->tfree_keys != 0));
     HIPCHK(c, hipEventRecord(c->ev_done[k], st));
     if (c->prof) {
       HIPCHK(c, hipEventRecord(ev.d, st));
@@ -727,7 +761,9 @@ int mbft_add_role(mbft_ctx* c, uint32_t role) {
 }
 
 int mbft_set_key_window(mbft_ctx* c, int wbits) {
-  if (!c || wbits < mbft_launch::kMinWindow || wbits > mbft_launch::kMaxWindow)
+  // (0, MBFT_WINDOW_NONE: keys registered from now on get no table)
+  if (!c || (wbits != mbft_launch::kWindowNone &&
+             (wbits < mbft_launch::kMinWindow || wbits > mbft_launch::kMaxWindow)))
     return MBFT_ERR_ARG;
   KeyWriteGuard g(c);
   c->q_wbits = wbits;
@@ -887,6 +923,9 @@ int mbft_clear_keys(mbft_ctx* c) {
     c->free_blocks.emplace_back(c->tab_blocks[i], c->tab_sizes[i]);
   c->tab_blocks.clear();
   c->tab_sizes.clear();
+  c->tfree_chunk = nullptr;  // (its block went with the others)
+  c->tfree_left = 0;
+  c->tfree_keys = 0;
   c->slots.clear();
   c->slot_of_xy.clear();
   c->keydesc.clear();

@@ -391,6 +391,16 @@ struct mbft_ctx {
   std::vector<size_t> tab_sizes;  // bytes of each tab_blocks entry
   std::vector<mbft::KeyDesc> keydesc;
   mbft_host::DevBuf d_keys;
+  // Table-free keys (key window 0): a key's whole device state is its point as
+  // one 64-byte comb entry, in pooled blocks (tab_blocks too) -- a registration
+  // call with many keys takes one block of its own, smaller calls draw from
+  // chunks of kTfreeChunk entries (tfree_chunk: the next free entry, tfree_left
+  // entries after it).  tfree_keys: valid slots with window 0; while it is
+  // zero a verify launches no table-free kernel.
+  static constexpr size_t kTfreeChunk = 4096;
+  uint32_t* tfree_chunk = nullptr;
+  size_t tfree_left = 0;
+  size_t tfree_keys = 0;
 
   // Multi-GPU in one process (mbft_ctx_add_device): peer engines on other
   // devices hold replicas of the comb tables (same slot numbering, same

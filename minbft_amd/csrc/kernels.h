@@ -6,7 +6,8 @@
 
 namespace mbft {
 // Per key slot, read by k_verify (16 B): the key's comb table, its window and
-// whether the key passed validation.
+// whether the key passed validation.  A table-free key (window 0): tab is the
+// point as one comb entry, wbits 0.
 struct KeyDesc {
   const uint32_t* tab;
   uint32_t wbits;
@@ -159,6 +160,10 @@ hipError_t prepare_calls(const PrepArgs& a, hipStream_t st);
 // scalar, 0.25 MiB; 16 -> 16 additions, 34 MiB; 20 -> 13, 388 MiB;
 // 22 -> 12, 1.4 GiB; 24 -> 11, 5.0 GiB; 26 -> 10, 18.3 GiB; 29 -> 9, 129 GiB.
 constexpr int kMinWindow = 4, kMaxWindow = 29;
+// Key window 0 (MBFT_WINDOW_NONE): no table.  The key's KeyDesc.tab points at
+// the point itself, ONE entry, and wbits is 0 (ladder_dev.h).  Keys only:
+// the generator always has a comb.
+constexpr int kWindowNone = 0;
 size_t table_entries(int wbits);
 size_t table_words(int wbits);
 int table_steps(int wbits);
@@ -172,6 +177,9 @@ hipError_t request_e(const uint64_t* seq, const uint8_t* ops, uint32_t op_len, l
                      hipStream_t st);
 hipError_t authen_e(const uint8_t* H, const AuthenDesc* d, long n, uint8_t* e, hipStream_t st);
 hipError_t check_points(const uint32_t* xy, int n, uint32_t* ok, hipStream_t st);
+// n validated points -> n comb entries (16 words each): a table-free key's
+// whole device state (key window 0)
+hipError_t point_entries(const uint32_t* xy, int n, uint32_t* out, hipStream_t st);
 hipError_t build_tables(const uint32_t* xy, int npts, int wbits, uint32_t* bpts, uint32_t* tab,
                         hipStream_t st);
 hipError_t generator_xy(uint32_t* xy16, hipStream_t st);
@@ -194,8 +202,8 @@ hipError_t sign(const uint8_t* priv, const uint32_t* key_idx, const uint8_t* e, 
                 long n, const uint32_t* tabG, int wg, uint8_t* r_out, uint8_t* s_out,
                 hipStream_t st);
 // words of the `slowq` buffer verify() needs for n items (exact-path queue,
-// its length, the rare comb steps' scratch; `pairs`: the small-batch kernels,
-// up to four threads per item)
+// the table-free queue, their lengths, the rare comb steps' scratch; `pairs`:
+// the small-batch kernels, up to four threads per item)
 size_t verify_words(long n, bool pairs = false);
 size_t verify_scratch_offset(long n);
 hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const uint32_t* slot,
@@ -203,9 +211,11 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
                   uint32_t nslots, long n, uint8_t* status, uint32_t* slowq, hipStream_t st,
                   bool host_status = false, bool queue_zeroed = false, long split_max = -1,
                   bool split_winv = false, const uint32_t* ndev = nullptr,
-                  uint32_t* planes_ws = nullptr, int small_form = -1);
+                  uint32_t* planes_ws = nullptr, int small_form = -1, bool table_free = false);
 // (planes_ws: 9 n words the small-batch forms may use for the batched s^-1
-// planes; small_form: their form, mbft_set_small_batch_inverse's modes)
+// planes; small_form: their form, mbft_set_small_batch_inverse's modes;
+// table_free: some key slot has window 0 -- k_verify queues such items and
+// k_verify_ladder follows it; the small-batch forms serve them in place)
 // The resident verifier: one 256-thread workgroup per mailbox slot, or two
 // (`two`: one per scalar, each on its own CU).
 hipError_t verify_server(const mbft::ServerArgs& a, int servers, bool two, hipStream_t st);

@@ -28,6 +28,7 @@
 #include "env.h"
 
 #include "kernels.h"
+#include "ladder_dev.h"
 #include "modinv.h"
 #include "scalar_dev.h"
 #include "sha256.h"
@@ -102,6 +103,25 @@ __global__ void k_check_points(const uint32_t* __restrict__ xy, int n,
   fe_canon(lhs);
   fe_canon(rhs);
   ok[i] = (in_range && fe_eq_canon(lhs, rhs)) ? 1u : 0u;
+}
+
+// A table-free key's whole device state (key window 0): the point as ONE comb
+// entry -- x, y as 8 + 8 LE words, canonical Montgomery -- which the ladder
+// reads (ladder_dev.h).  xy: n validated plain affine points, 16 LE words each.
+__global__ void k_point_entries(const uint32_t* __restrict__ xy, int n, uint32_t* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t wx[8], wy[8];
+  load_words8(wx, xy + 16 * i);
+  load_words8(wy, xy + 16 * i + 8);
+  fe x, y;
+  fe_from_words(x, wx);
+  fe_from_words(y, wy);
+  fe_to_mont(x, x);
+  fe_to_mont(y, y);
+  fe_canon(x);
+  fe_canon(y);
+  store_point_words(out + 16 * i, x, y);
 }
 
 // Comb geometry for window W, SIGNED digits: S = ceil(256 / W) windows.  A
@@ -742,12 +762,23 @@ struct VerifyArgs {
   uint8_t* status;
   uint32_t* slowq;         // exact-path queue: item indices (n entries)
   uint32_t* slown;         // its length (zeroed before k_verify)
-  uint32_t host_status;    // slots >= kHostSlot carry the host's status (batch pipeline)
+  uint32_t host_status;    // bit 0: slots >= kHostSlot carry the host's status (batch pipeline);
+                           // bit 1 (kArgTableFree): the context holds a table-free key -- the
+                           // second queue (ladder_queue, ladder_count) is live
   uint32_t* scr;           // per-thread spill of the rare comb steps: 36 planes of sstride words
   uint32_t sstride;        // = threads in the grid
   const uint32_t* ndev;    // optional (small-batch kernels): the item count on the device, <= n
   const uint32_t* uhost = nullptr;  // optional (k_verify_split): u1, u2 per item, 16 LE words (host)
 };
+constexpr uint32_t kArgHostStatus = 1u, kArgTableFree = 2u;
+
+// The table-free items' queue (k_verify -> k_verify_ladder) inside the
+// `slowq` buffer (mbft_launch::verify_words): its length right after the
+// exact-path queue's, its n entries from the next 64-word boundary.  Derived
+// from slowq / slown, so the kernels' argument block is what it was.
+__host__ __device__ inline size_t ladder_queue_offset(long n) { return ((size_t)n + 2 + 63) & ~(size_t)63; }
+MBFT_DEV uint32_t* ladder_count(const VerifyArgs& A) { return A.slown + 1; }
+MBFT_DEV uint32_t* ladder_queue(const VerifyArgs& A) { return A.slowq + ladder_queue_offset(A.n); }
 
 constexpr uint8_t ST_ACCEPT = 0, ST_REJECT = 1, ST_BAD_KEY = 5;
 
@@ -1364,6 +1395,40 @@ MBFT_DEV void verify_exact(const VerifyArgs& A, long i) {
   verify_finish(A, i, j.X, ZZ);
 }
 
+// Item i under a table-free key (KeyDesc.wbits == 0: `tab` is the point
+// itself, one comb entry): u2 Q by the ladder (ladder_dev.h), then u1 G's
+// comb entries added to it one by one with complete additions -- every join
+// case (u1 G == +-u2 Q, the keys Q == +-G, u1 == 0) is exact, and the G side
+// is ~4 % of the item's work.  r, s in range and the key valid (the caller
+// checked).  A final infinity rejects, as Go's (0, 0) does.
+template <bool LANE_INV>
+MBFT_DEV void verify_ladder_item(const VerifyArgs& A, long i) {
+  const KeyDesc kd = A.keys[A.slot[i]];
+  uint32_t U1[8], U2[8];
+  load_scalars<LANE_INV>(A, i, U1, U2);
+  fe qx, qy;
+  load_point(qx, qy, reinterpret_cast<const uint4*>(kd.tab));
+  bool inf = true;
+  jac j;
+  ladder_mul(j, inf, U2, qx, qy);
+  comb_complete(j, inf, U1, A.tabG, A.wg);
+  if (inf) {
+    A.status[i] = ST_REJECT;  // (x, y) = (0, 0) -> false
+    return;
+  }
+  fe ZZ;
+  fe_sqr(ZZ, j.Z);
+  verify_finish(A, i, j.X, ZZ);
+}
+
+// (the small-batch forms: s^-1 from the planes where the batch has them)
+MBFT_DEV void verify_ladder_inline(const VerifyArgs& A, long i) {
+  if (A.winv)
+    verify_ladder_item<false>(A, i);
+  else
+    verify_ladder_item<true>(A, i);
+}
+
 // One item per thread.  Every lane of the wave runs the comb loop (the
 // cooperative gather needs all 64): lanes past the end of the batch, with an
 // unknown / invalid key, or with r or s out of range are "dead" -- they run
@@ -1386,9 +1451,26 @@ MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf,
   const bool key_ok = slot < A.nslots && kd.valid;
   // slots >= kHostSlot carry a status the host decided (batch pipeline):
   // written as is, so the statuses the host reads back are final
+  // a table-free key (window 0): not live for the comb; its index goes to the
+  // second compacted queue, which k_verify_ladder serves (one atomic per
+  // wave) and whose status is that kernel's to write (kNoStatus here)
+  constexpr uint8_t kNoStatus = 0xFF;
+  const bool tfree = key_ok && kd.wbits == 0u;
+  const bool queued = tfree && in_batch && range_ok && (A.host_status & kArgTableFree);
   const uint8_t dead_status =
-      key_ok ? ST_REJECT : (A.host_status && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
-  const bool live = in_batch && key_ok && range_ok;
+      queued ? kNoStatus
+             : key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
+  const bool live = in_batch && key_ok && range_ok && !tfree;
+  if (queued) {
+    const uint64_t qm = __ballot(true);
+    const int nq = __popcll(qm);
+    const int rank = __popcll(qm & ((1ull << __lane_id()) - 1ull));
+    const int leader = __ffsll((unsigned long long)qm) - 1;
+    uint32_t base = 0;
+    if (__lane_id() == leader) base = atomicAdd(ladder_count(A), (uint32_t)nq);
+    base = __shfl(base, leader);
+    ladder_queue(A)[base + rank] = (uint32_t)i;
+  }
 
   // w = s^-1 (Montgomery form), u1 = e w, u2 = r w (plain, canonical < N).
   // e, r, w are not kept live across the comb (register pressure): the rare
@@ -1402,11 +1484,11 @@ MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf,
 
   // Dead lanes adopt the first live lane's key table; the Q phase gathers
   // cooperatively when every lane then has the same key window.
+  // (a dead lane's status is written here, before the comb, so that nothing
+  // of it stays live across the comb)
+  if (!live && in_batch && dead_status != kNoStatus) A.status[i] = dead_status;
   const uint64_t lm = __ballot(live);
-  if (lm == 0) {
-    if (in_batch) A.status[i] = dead_status;
-    return;
-  }
+  if (lm == 0) return;
   const int first = __ffsll((unsigned long long)lm) - 1;
   const uint64_t tq64 = reinterpret_cast<uint64_t>(tq);
   const uint32_t tlo = __builtin_amdgcn_readlane((uint32_t)tq64, first);
@@ -1454,10 +1536,7 @@ MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf,
     }
   } end_stamp{tv0};
 #endif
-  if (!live) {
-    if (in_batch) A.status[i] = dead_status;
-    return;
-  }
+  if (!live) return;
   if (inf) {
     A.status[i] = ST_REJECT;  // u1 G + u2 Q = infinity: (x, y) = (0, 0) -> false
     return;
@@ -1507,8 +1586,11 @@ MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, 
   if (slot < A.nslots) kd = A.keys[slot];
   const bool key_ok = slot < A.nslots && kd.valid;
   const uint8_t dead_status =
-      key_ok ? ST_REJECT : (A.host_status && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
-  const bool live = in_batch && key_ok && range_ok;
+      key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
+  // a table-free key (window 0) takes no part in the comb: its even lane
+  // runs the ladder at the end
+  const bool tfree = key_ok && kd.wbits == 0u;
+  const bool live = in_batch && key_ok && range_ok && !tfree;
   uint32_t U1[8], U2[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) U1[j] = U2[j] = 0u;
@@ -1592,7 +1674,10 @@ MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, 
   const bool oyneg = __shfl_xor(yneg ? 1 : 0, 1) != 0;
   if (qh) return;
   if (!live) {
-    if (in_batch) A.status[i] = dead_status;
+    if (in_batch && tfree && range_ok)
+      verify_ladder_inline(A, i);
+    else if (in_batch)
+      A.status[i] = dead_status;
     return;
   }
   fe X, ZZ;
@@ -1648,8 +1733,11 @@ MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uin
   if (slot < A.nslots) kd = A.keys[slot];
   const bool key_ok = slot < A.nslots && kd.valid;
   const uint8_t dead_status =
-      key_ok ? ST_REJECT : (A.host_status && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
-  const bool live = in_batch && key_ok && range_ok;
+      key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
+  // a table-free key (window 0) takes no part in the comb: its even lane
+  // runs the ladder at the end
+  const bool tfree = key_ok && kd.wbits == 0u;
+  const bool live = in_batch && key_ok && range_ok && !tfree;
   uint32_t U1[8], U2[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) U1[j] = U2[j] = 0u;
@@ -1775,7 +1863,10 @@ MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uin
   const bool qdegen = __shfl_xor(degen ? 1 : 0, 2) != 0;
   if (qh) return;
   if (!live) {
-    if (in_batch) A.status[i] = dead_status;
+    if (in_batch && tfree && range_ok)
+      verify_ladder_inline(A, i);
+    else if (in_batch)
+      A.status[i] = dead_status;
     return;
   }
   if (degen || qdegen) {
@@ -1981,7 +2072,10 @@ extern "C" int mbft_debug_split_timing(unsigned long long out[162]) {
 // host computed them): u1, u2 as 16 LE words, loaded with the other inputs,
 // so the waves skip s^-1 and the two mod-N products (~3 us of a lone call's
 // critical path on one wave).
-template <bool WIDE, int NP = 4>
+// TFREE: table-free keys are served (thread 0 runs the ladder); the resident
+// kernel's instances are not (resident.cpp keeps such keys off the mailbox:
+// a slot that held one would read BAD_KEY).
+template <bool WIDE, int NP = 4, bool TFREE = true>
 MBFT_DEV void split_item(const VerifyArgs& A, long i, uint32_t (&part)[NP][4 * NL + 1],
                          uint4 (&pre)[4][4 * kSplitPre], uint32_t* pout = nullptr, int half = -1,
                          const uint32_t* uin = nullptr) {
@@ -2004,13 +2098,18 @@ MBFT_DEV void split_item(const VerifyArgs& A, long i, uint32_t (&part)[NP][4 * N
   const bool range_ok = !words_is_zero(rw) && words_lt(rw, kNw) && !words_is_zero(sw) && words_lt(sw, kNw);
   KeyDesc kd{A.tabG, (uint32_t)A.wg, 0u};
   if (slot < A.nslots) kd = A.keys[slot];
-  const bool key_ok = slot < A.nslots && kd.valid;
-  if (!(key_ok && range_ok)) {  // block-uniform: the whole workgroup returns
+  const bool tfree = slot < A.nslots && kd.valid && kd.wbits == 0u;
+  const bool key_ok = slot < A.nslots && kd.valid && (TFREE || !tfree);
+  if (!(key_ok && range_ok) || tfree) {  // block-uniform: the whole workgroup returns
     // the status last, after every wave has read the inputs: the host may
     // reuse zero-copy staging as soon as it sees it (batch.cpp spin_statuses)
     __syncthreads();
-    if (threadIdx.x == 0)
-      A.status[i] = key_ok ? ST_REJECT : (A.host_status && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
+    if (threadIdx.x == 0) {
+      if (TFREE && tfree && range_ok)
+        verify_ladder_inline(A, i);
+      else
+        A.status[i] = key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
+    }
     return;
   }
   SPLIT_T(1);
@@ -2368,12 +2467,12 @@ __global__ void __launch_bounds__(256) MBFT_SRV_ATTR k_verify_server(ServerArgs 
       // many items at once, whose joins would queue on the caller's one
       // thread; the second job only answers
       if (!TWO || h == 0)
-        split_item<WIDE, 4>(A, 0, *reinterpret_cast<uint32_t(*)[4][4 * NL + 1]>(&part[0][0]), pre, nullptr, -1,
+        split_item<WIDE, 4, false>(A, 0, *reinterpret_cast<uint32_t(*)[4][4 * NL + 1]>(&part[0][0]), pre, nullptr, -1,
                             it->ugiven ? it->u : nullptr);
       else if (threadIdx.x == 0)
         st_lds[0] = kSrvPartials;
     } else {
-      split_item<WIDE, NP>(A, 0, part, pre, S.ctl->part[b] + (TWO ? 40 * NP * h : 0), TWO ? (int)h : -1,
+      split_item<WIDE, NP, false>(A, 0, part, pre, S.ctl->part[b] + (TWO ? 40 * NP * h : 0), TWO ? (int)h : -1,
                            it->ugiven ? it->u : nullptr);
     }
     __syncthreads();
@@ -2458,6 +2557,22 @@ __global__ void __launch_bounds__(256, 2) k_verify_slow(VerifyArgs A) {
     const bool in = q < nq;
     verify_pair<false>(A, in ? (long)A.slowq[q] : 0, (int)(t & 1), in, buf, sp);
   }
+}
+
+// The items k_verify queued for their table-free keys (window 0): one item
+// per lane, grid-stride over the second compacted queue (its length is known
+// only on the device; an empty queue ends the kernel at once).  u2 Q by the
+// double-and-add ladder, s^-1 from the batch's planes, u1 G added with
+// complete additions (verify_ladder_item).  Not served as G / Q lane pairs:
+// the G half is a few percent of an item's work, and the pair would idle
+// half the lanes.
+__global__ void __launch_bounds__(256, 2) k_verify_ladder(VerifyArgs A) {
+  long nq = (long)*ladder_count(A);
+  if (nq > A.n) nq = A.n;  // (the queue holds n entries)
+  const long stride = (long)gridDim.x * blockDim.x;
+#pragma unroll 1
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += stride)
+    verify_ladder_item<false>(A, (long)ladder_queue(A)[q]);
 }
 
 #ifdef MBFT_CLOCK_STAMP
@@ -2943,6 +3058,12 @@ hipError_t check_points(const uint32_t* xy, int n, uint32_t* ok, hipStream_t st)
   return hipGetLastError();
 }
 
+hipError_t point_entries(const uint32_t* xy, int n, uint32_t* out, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_point_entries, dim3((n + 127) / 128), dim3(128), 0, st, xy, n, out);
+  return hipGetLastError();
+}
+
 size_t table_entries(int wbits) {
   const int S = (256 + wbits - 1) / wbits;
   return ((size_t)(S - 1) << (wbits - 1)) + ((size_t)1 << (256 - (S - 1) * wbits));
@@ -3113,9 +3234,12 @@ hipError_t sign(const uint8_t* priv, const uint32_t* key_idx, const uint8_t* e, 
 }
 
 // The verifier's queue + scratch buffer: the exact-path queue (n words), its
-// length, then (64-word aligned) 36 planes of one word per grid thread for
-// the rare comb steps' spills (comb_run).
-size_t verify_scratch_offset(long n) { return ((size_t)n + 1 + 63) & ~(size_t)63; }
+// length, the table-free queue's length (the two counters side by side: one
+// memset zeroes both), then (64-word aligned) the table-free queue (n words)
+// and (64-word aligned) 36 planes of one word per grid thread for the rare
+// comb steps' spills (comb_run).  Both queues are there for every path,
+// whatever form the batch takes.
+size_t verify_scratch_offset(long n) { return (ladder_queue_offset(n) + (size_t)n + 63) & ~(size_t)63; }
 size_t verify_words(long n, bool pairs) {
   // (small batches: room for k_verify_quads' 4 threads an item)
   const size_t threads = (size_t)(pairs ? 4 * n : n);
@@ -3151,7 +3275,7 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
                   const uint32_t* winv, const uint32_t* tabG, int wg, const KeyDesc* keys,
                   uint32_t nslots, long n, uint8_t* status, uint32_t* slowq, hipStream_t st,
                   bool host_status, bool queue_zeroed, long split_max, bool split_winv,
-                  const uint32_t* ndev, uint32_t* planes_ws, int small_form) {
+                  const uint32_t* ndev, uint32_t* planes_ws, int small_form, bool table_free) {
   if (n <= 0) return hipSuccess;
   // slowq: n + 1 words (the queue, then its length)
   VerifyArgs A{e, r, s, slot, winv, tabG, keys, nslots, wg, n, status, slowq, slowq + n,
@@ -3195,10 +3319,14 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
     A.uhost = nullptr;
   }
   // small batches (winv null) run the exact path inline: no queue to reset
-  if (winv && !queue_zeroed) {
-    hipError_t me = hipMemsetAsync(slowq + n, 0, 4, st);
+  // table_free (the context holds a table-free key): the second queue's
+  // counter, next to the first, is zeroed here in any case
+  if (winv && (!queue_zeroed || table_free)) {
+    hipError_t me = queue_zeroed ? hipMemsetAsync(slowq + n + 1, 0, 4, st)
+                                 : hipMemsetAsync(slowq + n, 0, table_free ? 8 : 4, st);
     if (me != hipSuccess) return me;
   }
+  if (table_free) A.host_status |= kArgTableFree;
   static const int bpc = (int)env_long("MBFT_VERIFY_BPC", 0);
   static const int ncu = [] {
     int dev = 0, cus = 256;
@@ -3253,6 +3381,12 @@ hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const ui
   long sblocks = (n + 255) / 256 < (long)ncu * kSlowBpc ? (n + 255) / 256 : (long)ncu * kSlowBpc;
   if (sblocks > blocks) sblocks = blocks;  // its threads index the same spill planes (A.sstride)
   if (winv) hipLaunchKernelGGL(k_verify_slow, dim3((unsigned)sblocks), dim3(256), 0, st, A);
+  // the table-free items: two blocks per CU at the most (the kernel's
+  // occupancy), grid-stride over the queue
+  if (winv && table_free) {
+    const long lblocks = (n + 255) / 256 < (long)ncu * 2 ? (n + 255) / 256 : (long)ncu * 2;
+    hipLaunchKernelGGL(k_verify_ladder, dim3((unsigned)lblocks), dim3(256), 0, st, A);
+  }
   return hipGetLastError();
 }
 

@@ -507,6 +507,9 @@ int resident_call(mbft_ctx* c, const mbft_item& it, uint8_t* st) {
     g = (uint8_t)(key & 0xFF);  // decided on the host (the USIG epoch step below decides)
   } else if (ci.pre == 0xFF) {
     if (key >= c->keydesc.size()) return fail(c, MBFT_ERR_STATE, "resident verifier: key slot");
+    // a table-free key (window 0) is the ladder's, which the mailbox kernel
+    // does not carry: the ordinary single-call path serves it
+    if (c->keydesc[key].valid && c->keydesc[key].wbits == 0u) return kNoResident;
 #ifdef MBFT_SRV_TIMING
     const double tt1 = now_ms();
 #endif
@@ -578,6 +581,8 @@ int resident_check(mbft_ctx* c, const mbft_item* items, size_t n, uint8_t* gst,
       gst[i] = (uint8_t)(key[i] & 0xFF);
     } else {
       if (key[i] >= c->keydesc.size()) return fail(c, MBFT_ERR_STATE, "resident verifier: key slot");
+      // (a table-free key: the whole check takes the ordinary path, as above)
+      if (c->keydesc[key[i]].valid && c->keydesc[key[i]].wbits == 0u) return kNoResident;
       gpu[m++] = i;
     }
   }
