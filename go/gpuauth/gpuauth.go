@@ -93,6 +93,15 @@ type Config struct {
 	// sets (INTEGRATION.md); ClientWindow is ignored.  A flag, since the
 	// zero value of the window fields means "default".
 	TableFreeClients bool
+	// ClientTeeth (2..8) registers client keys -- those given to New and
+	// those registered late from KeyStore -- as COMPACT keys
+	// (mbft_set_key_teeth): a table of 2^ClientTeeth entries of 64 bytes per
+	// key (256 B at 2, 1 KiB at 4, 16 KiB at 8), verified by a comb with
+	// doublings at a fraction of the table-free ladder's cost.  Between
+	// TableFreeClients and the smallest comb window (32 KiB a key) for a
+	// large client set (INTEGRATION.md).  Zero: not used.  It wins over
+	// ClientWindow and TableFreeClients; a value outside 2..8 fails New.
+	ClientTeeth int
 	// Private keys of the ECDSA roles this node signs as (CPU signing with
 	// the reference scheme, crypto.go:63-76), used when Generator is nil.
 	PrivateKeys map[api.AuthenticationRole]*ecdsa.PrivateKey
@@ -208,15 +217,8 @@ func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnable
 		if roleByte(role) == 0 {
 			continue // no scheme for the role (authenticator.go:126-129): its calls are rejected anyway
 		}
-		kw := w.Replica
-		switch role {
-		case api.ClientAuthen:
-			kw = w.Client
-		case api.USIGAuthen:
-			kw = w.USIG
-		}
-		if rc := C.mbft_set_key_window(ctx, C.int(kw)); rc != C.MBFT_OK {
-			return fail("mbft_set_key_window", rc)
+		if rc := setKeyClass(ctx, w, role); rc != C.MBFT_OK {
+			return fail("mbft_set_key_window / mbft_set_key_teeth", rc)
 		}
 		C.mbft_add_role(ctx, C.uint32_t(role))
 		for id, pk := range m {
@@ -315,9 +317,26 @@ func KeysFromStore(ks PublicKeyStore, ids map[api.AuthenticationRole][]uint32) (
 	return keys, nil
 }
 
-// Windows are the comb windows per key class (bits).
+// Windows are the comb windows per key class (bits).  ClientTeeth != 0: the
+// client keys are compact keys with that many teeth (Client is then 0).
 type Windows struct {
 	Generator, Replica, USIG, Client int
+	ClientTeeth                      int
+}
+
+// setKeyClass selects the class of the keys registered next for role: the
+// role's window, or the compact class for clients when ClientTeeth is set.
+func setKeyClass(ctx *C.mbft_ctx, w Windows, role api.AuthenticationRole) C.int {
+	switch role {
+	case api.ClientAuthen:
+		if w.ClientTeeth != 0 {
+			return C.mbft_set_key_teeth(ctx, C.int(w.ClientTeeth))
+		}
+		return C.mbft_set_key_window(ctx, C.int(w.Client))
+	case api.USIGAuthen:
+		return C.mbft_set_key_window(ctx, C.int(w.USIG))
+	}
+	return C.mbft_set_key_window(ctx, C.int(w.Replica))
 }
 
 // DefaultWindows sizes the comb tables from the device's HBM and the key
@@ -327,8 +346,8 @@ type Windows struct {
 func DefaultWindows(nkeys map[api.AuthenticationRole]int, cfg Config) Windows {
 	var g, r, u, c C.int
 	nclients := nkeys[api.ClientAuthen]
-	if cfg.TableFreeClients {
-		nclients = 0
+	if cfg.TableFreeClients || cfg.ClientTeeth != 0 {
+		nclients = 0 // (compact tables are at most 16 KiB a key: left out of the plan)
 	}
 	C.mbft_plan_windows(C.int(firstDevice(cfg)), C.size_t(nkeys[api.ReplicaAuthen]),
 		C.size_t(nkeys[api.USIGAuthen]), C.size_t(nclients), &g, &r, &u, &c)
@@ -340,6 +359,10 @@ func DefaultWindows(nkeys map[api.AuthenticationRole]int, cfg Config) Windows {
 	}
 	if cfg.TableFreeClients {
 		w.Client = int(C.MBFT_WINDOW_NONE)
+	}
+	if cfg.ClientTeeth != 0 {
+		w.Client = int(C.MBFT_WINDOW_NONE) // what mbft_get_windows reports for the class
+		w.ClientTeeth = cfg.ClientTeeth
 	}
 	return w
 }

@@ -114,16 +114,6 @@ func (r *keyRegistry) add(role api.AuthenticationRole, id uint32) {
 	r.mu.Unlock()
 }
 
-func (r *keyRegistry) window(role api.AuthenticationRole) int {
-	switch role {
-	case api.ClientAuthen:
-		return r.windows.Client
-	case api.USIGAuthen:
-		return r.windows.USIG
-	}
-	return r.windows.Replica
-}
-
 // ensure makes sure (role, id) is registered if the key store has a key for
 // it.  Cheap when it is known or known absent (a read-locked map lookup).
 func (a *Authenticator) ensureKey(role api.AuthenticationRole, id uint32) {
@@ -169,7 +159,7 @@ func (a *Authenticator) ensureKey(role api.AuthenticationRole, id uint32) {
 	}
 	// the context-wide "window for keys registered next": set under r.mu,
 	// the only place keys are added after New
-	if C.mbft_set_key_window(a.ctx, C.int(r.window(role))) != C.MBFT_OK {
+	if setKeyClass(a.ctx, r.windows, role) != C.MBFT_OK {
 		return // left unknown: the call is rejected as with no key, retried next time
 	}
 	C.mbft_add_role(a.ctx, C.uint32_t(role))

@@ -195,6 +195,32 @@ int mbft_key_slot(const mbft_ctx* ctx, uint32_t role, uint32_t id);
 int mbft_set_key_window(mbft_ctx* ctx, int wbits);
 int mbft_set_generator_window(mbft_ctx* ctx, int wbits);
 int mbft_get_windows(const mbft_ctx* ctx, int* g_wbits, int* q_wbits);
+/* COMPACT keys: between the table-free class (64 B a key) and the smallest
+ * comb window (32 KiB a key at W = 4).  mbft_set_key_teeth(ctx, t), t in
+ * MBFT_TEETH_MIN .. MBFT_TEETH_MAX, gives keys registered AFTER the call a
+ * small table of 2^t entries of 64 B (in pooled blocks), verified by a comb
+ * WITH doublings (Lim-Lee): d = ceil(256 / t) columns, d - 1 doublings and at
+ * most d additions a signature.  Memory per key and field reductions for
+ * u2 Q, counted from the formulas (doubling 8, mixed addition 10), against
+ * about 2,900 for the table-free ladder and about 170 for a whole W = 29
+ * verify:
+ *   t = 2: 256 B, ~1,980 (0.68 of the ladder)   t = 6:  4 KiB, ~760 (0.26)
+ *   t = 3: 512 B, ~1,430 (0.49)                 t = 8: 16 KiB, ~570 (0.20)
+ *   t = 4: 1 KiB, ~1,100 (0.38)
+ * A million clients at t = 4 take 1 GiB.  DESIGN.md §4.8 has the measured
+ * rates.  Any other t is MBFT_ERR_ARG; MBFT_ERR_NOMEM at registration if the
+ * tables do not fit (the slots stay invalid).  A later mbft_set_key_window
+ * -- MBFT_WINDOW_NONE included -- switches back to windows; its accepted
+ * range is what it was.  While teeth are selected mbft_get_windows reports
+ * key window 0 and mbft_get_key_teeth reports t; mbft_get_key_teeth reports
+ * 0 while the current class is a window.  Every verify entry point serves
+ * such keys (the resident verifier hands them to the ordinary path), and
+ * keys of every class -- windows 4..29, window 0, teeth 2..8 -- live side by
+ * side in one context. */
+#define MBFT_TEETH_MIN 2
+#define MBFT_TEETH_MAX 8
+int mbft_set_key_teeth(mbft_ctx* ctx, int teeth);        /* keys registered AFTER the call */
+int mbft_get_key_teeth(const mbft_ctx* ctx, int* teeth); /* 0 while the current class is a window */
 /* USIG scheme present (authenticator.go:102-110: absent without a USIG). */
 int mbft_enable_usig(mbft_ctx* ctx, int enabled);
 /* Private key for GenerateMessageAuthenTag in an ECDSA role. */

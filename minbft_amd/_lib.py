@@ -44,6 +44,8 @@ ROLE_CLIENT = 3
 
 #: key window of table-free keys (MBFT_WINDOW_NONE)
 WINDOW_NONE = 0
+#: teeth of compact keys (MBFT_TEETH_MIN, MBFT_TEETH_MAX)
+TEETH_MIN, TEETH_MAX = 2, 8
 
 #: bytes per tag slot of the batch signer (MBFT_TAG_SLOT)
 TAG_SLOT = 72
@@ -79,6 +81,7 @@ EXPORTED = [
     "mbft_sign_messages_flat", "mbft_set_signer_window",
     "mbft_usig_init", "mbft_usig_id", "mbft_usig_next_counter", "mbft_usig_create_uis_digests",
     "mbft_usig_create_uis_flat", "mbft_usig_sign_messages_flat",
+    "mbft_set_key_teeth", "mbft_get_key_teeth",
 ]
 
 # enum mbft_msg_type / mbft_stage / mbft_validate_flags
@@ -227,6 +230,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_enable_usig": (i, [vp, i]),
         "mbft_set_key_window": (i, [vp, i]),
         "mbft_set_generator_window": (i, [vp, i]),
+        "mbft_set_key_teeth": (i, [vp, i]),
+        "mbft_get_key_teeth": (i, [vp, ctypes.POINTER(i)]),
         "mbft_get_windows": (i, [vp, ctypes.POINTER(i), ctypes.POINTER(i)]),
         "mbft_request_digests_device": (i, [vp, vp, vp, u32, sz, vp, vp]),
         "mbft_sha256_device": (i, [vp, vp, vp, sz, vp, vp]),

@@ -177,6 +177,20 @@ class Authenticator:
         verified by a double-and-add ladder (open or very large client sets)."""
         self._check(self.lib.mbft_set_key_window(self.ctx, wbits), "set_key_window")
 
+    def set_key_teeth(self, teeth: int):
+        """Compact keys for keys registered after the call: a table of
+        ``2**teeth`` entries of 64 bytes per key (``teeth`` in 2..8: 256 B to
+        16 KiB), verified by a comb with doublings -- between table-free keys
+        and the smallest comb window (include/minbft_gpu.h lists the cost).
+        A later ``set_key_window`` switches back to windows."""
+        self._check(self.lib.mbft_set_key_teeth(self.ctx, teeth), "set_key_teeth")
+
+    def key_teeth(self) -> int:
+        """Teeth of the compact class while it is selected, else 0."""
+        t = ctypes.c_int()
+        self._check(self.lib.mbft_get_key_teeth(self.ctx, ctypes.byref(t)), "get_key_teeth")
+        return t.value
+
     def set_generator_window(self, wbits: int):
         """Rebuild the generator comb table with a window of 4..29 bits."""
         self._check(self.lib.mbft_set_generator_window(self.ctx, wbits), "set_generator_window")

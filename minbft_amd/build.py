@@ -32,7 +32,8 @@ HOST_SOURCES = ["host.cpp", "der.cpp", "messages.cpp", "batch.cpp", "msgdev.cpp"
 HEADERS = ["fe29.h", "ecc.h", "modinv.h", "der_dev.h", "sha256.h", "sha256_dev.h", "authen_dev.h", "arena_dev.h",
            "kernels.h", "scalar_dev.h", "env.h",
            "msg_dev.h", "host_internal.h", "join_core.inc",
-           "sign_dev.h", "der_enc_dev.h", "sign_kernels.h", "sign_rs_dev.h", "ladder_dev.h"]
+           "sign_dev.h", "der_enc_dev.h", "sign_kernels.h", "sign_rs_dev.h", "ladder_dev.h",
+           "teeth_dev.h"]
 
 
 def _hipcc() -> str:

@@ -224,6 +224,16 @@ uint64_t fingerprint_of(const uint8_t xy[64]) {
   return f;
 }
 
+// The class of keys registered from now on as KeyDesc.wbits carries it: the
+// key window (0: table-free), or kTeethFlag | t for compact keys.
+uint32_t key_class(const mbft_ctx* c) {
+  return c->q_teeth ? (mbft::kTeethFlag | (uint32_t)c->q_teeth) : (uint32_t)c->q_wbits;
+}
+void set_key_class(mbft_ctx* c, uint32_t cls) {
+  c->q_teeth = cls >= mbft::kTeethFlag ? (int)(cls & 0xFFu) : 0;
+  c->q_wbits = cls >= mbft::kTeethFlag ? mbft_launch::kWindowNone : (int)cls;
+}
+
 // Register (dedup) raw points on ONE engine; validates on the GPU and builds
 // comb tables.
 int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t* out_slots,
@@ -283,13 +293,51 @@ int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t*
       si.fp_group = fg.first->second;
       c->slots.push_back(si);
       c->slot_of_xy[si.xy] = (uint32_t)(base + j);
-      c->keydesc.push_back(mbft::KeyDesc{nullptr, (uint32_t)c->q_wbits, 0u});
+      c->keydesc.push_back(mbft::KeyDesc{nullptr, key_class(c), 0u});
       if (si.valid) {
         vwords.insert(vwords.end(), &words[16 * j], &words[16 * j] + 16);
         vslots.push_back((uint32_t)(base + j));
       }
     }
-    if (!vslots.empty() && c->q_wbits == mbft_launch::kWindowNone) {
+    if (!vslots.empty() && c->q_teeth) {
+      // compact keys: a table of 2^t entries each, pooled per t like the
+      // table-free entries
+      const int t = c->q_teeth;
+      const size_t cnt = vslots.size();
+      const size_t tw = mbft_launch::teeth_table_words(t);
+      const size_t per_chunk = mbft_ctx::kTeethChunk / (tw * 4);
+      uint32_t* dst = nullptr;
+      if (cnt <= c->teeth_left[t]) {
+        dst = c->teeth_chunk[t];
+      } else {
+        const size_t tabs = cnt >= per_chunk / 4 ? cnt : per_chunk;
+        hipError_t he = table_block(c, tabs * tw * 4, &dst);
+        if (he != hipSuccess) {
+          // keep the slots (invalid) so slot numbering stays consistent
+          (void)hipGetLastError();
+          return fail(c, MBFT_ERR_NOMEM, "compact keys: out of device memory (teeth " +
+                                             std::to_string(t) + ")");
+        }
+        if (tabs != cnt) {
+          c->teeth_chunk[t] = dst;
+          c->teeth_left[t] = tabs;
+        }
+      }
+      if (dst == c->teeth_chunk[t]) {
+        c->teeth_chunk[t] += tw * cnt;
+        c->teeth_left[t] -= cnt;
+      }
+      HIPCHK(c, c->xy.ensure(64 * cnt));
+      HIPCHK(c, hipMemcpyAsync(c->xy.p, vwords.data(), 64 * cnt, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, mbft_launch::build_teeth_tables(c->xy.as<uint32_t>(), (int)cnt, t, dst, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (size_t j = 0; j < cnt; j++) {
+        mbft::KeyDesc& kd = c->keydesc[vslots[j]];
+        kd.tab = dst + j * tw;
+        kd.valid = 1;
+      }
+      c->tfree_keys += cnt;
+    } else if (!vslots.empty() && c->q_wbits == mbft_launch::kWindowNone) {
       // table-free keys: each valid point as ONE comb entry, nothing else
       const size_t cnt = vslots.size();
       uint32_t* dst = nullptr;
@@ -510,7 +558,7 @@ int register_points(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t* out_sl
   for (mbft_ctx* p : c->peers) {
     std::lock_guard<std::mutex> g(p->mu);
     if (hipSetDevice(p->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice(peer)");
-    p->q_wbits = c->q_wbits;
+    set_key_class(p, key_class(c));
     rc = register_points_engine(p, xy64, n, nullptr, nullptr);
     if (rc) return fail(c, rc, std::string("peer engine: ") + p->err);
     if (p->slots.size() != c->slots.size()) return fail(c, MBFT_ERR_STATE, "peer slot mismatch");
@@ -767,6 +815,21 @@ int mbft_set_key_window(mbft_ctx* c, int wbits) {
     return MBFT_ERR_ARG;
   KeyWriteGuard g(c);
   c->q_wbits = wbits;
+  c->q_teeth = 0;  // (back from the compact class, if it was selected)
+  return MBFT_OK;
+}
+
+int mbft_set_key_teeth(mbft_ctx* c, int teeth) {
+  if (!c || teeth < mbft_launch::kTeethMin || teeth > mbft_launch::kTeethMax) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  c->q_teeth = teeth;
+  c->q_wbits = mbft_launch::kWindowNone;  // what mbft_get_windows reports meanwhile
+  return MBFT_OK;
+}
+
+int mbft_get_key_teeth(const mbft_ctx* c, int* teeth) {
+  if (!c) return MBFT_ERR_ARG;
+  if (teeth) *teeth = c->q_teeth;
   return MBFT_OK;
 }
 
@@ -803,7 +866,8 @@ int mbft_ctx_add_device(mbft_ctx* c, int device) {
   };
   rc = mbft_set_generator_window(p, c->g_wbits);
   if (rc) return bail(rc, "peer engine: " + p->err);
-  // replay every slot in order, in runs of equal key window
+  // replay every slot in order, in runs of equal key class (a window, or the
+  // compact class with its teeth: KeyDesc.wbits)
   const size_t ns = c->slots.size();
   size_t a = 0;
   (void)hipSetDevice(device);
@@ -812,13 +876,13 @@ int mbft_ctx_add_device(mbft_ctx* c, int device) {
     while (b < ns && c->keydesc[b].wbits == c->keydesc[a].wbits) b++;
     std::vector<uint8_t> xy(64 * (b - a));
     for (size_t j = a; j < b; j++) memcpy(&xy[64 * (j - a)], c->slots[j].xy.data(), 64);
-    p->q_wbits = (int)c->keydesc[a].wbits;
+    set_key_class(p, c->keydesc[a].wbits);
     rc = register_points_engine(p, xy.data(), b - a, nullptr, nullptr);
     if (rc) return bail(rc, "peer engine: " + p->err);
     a = b;
   }
   if (p->slots.size() != ns) return bail(MBFT_ERR_STATE, "peer slot mismatch");
-  p->q_wbits = c->q_wbits;
+  set_key_class(p, key_class(c));
   p->prof = false;
   p->split_max = c->split_max;
   p->small_inv = c->small_inv;
@@ -926,6 +990,10 @@ int mbft_clear_keys(mbft_ctx* c) {
   c->tfree_chunk = nullptr;  // (its block went with the others)
   c->tfree_left = 0;
   c->tfree_keys = 0;
+  for (int t = 0; t < 9; t++) {
+    c->teeth_chunk[t] = nullptr;
+    c->teeth_left[t] = 0;
+  }
   c->slots.clear();
   c->slot_of_xy.clear();
   c->keydesc.clear();

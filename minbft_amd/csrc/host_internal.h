@@ -401,6 +401,17 @@ struct mbft_ctx {
   uint32_t* tfree_chunk = nullptr;
   size_t tfree_left = 0;
   size_t tfree_keys = 0;
+  // Compact keys (mbft_set_key_teeth, teeth_dev.h): q_teeth != 0 selects the
+  // class for keys registered from now on (q_wbits is then 0, what
+  // mbft_get_windows reports).  A key's table of 2^t entries lies in pooled
+  // blocks by the same scheme, one chunk list per t: teeth_chunk[t] is the next
+  // free table, teeth_left[t] tables after it, a fresh chunk is kTeethChunk
+  // bytes.  Valid compact slots count into tfree_keys too: both classes are
+  // served from the second queue.
+  static constexpr size_t kTeethChunk = (size_t)1 << 20;
+  int q_teeth = 0;
+  uint32_t* teeth_chunk[9] = {};
+  size_t teeth_left[9] = {};
 
   // Multi-GPU in one process (mbft_ctx_add_device): peer engines on other
   // devices hold replicas of the comb tables (same slot numbering, same

@@ -7,12 +7,23 @@
 namespace mbft {
 // Per key slot, read by k_verify (16 B): the key's comb table, its window and
 // whether the key passed validation.  A table-free key (window 0): tab is the
-// point as one comb entry, wbits 0.
+// point as one comb entry, wbits 0.  A compact key (t teeth, teeth_dev.h): tab
+// is its table of 2^t entries, wbits kTeethFlag | t -- a class code, NOT a
+// window: whatever takes wbits as a comb window first rules it out with
+// key_class_queued.
 struct KeyDesc {
   const uint32_t* tab;
   uint32_t wbits;
   uint32_t valid;
 };
+constexpr uint32_t kTeethFlag = 0x100u;
+// The key classes that take no part in the comb: window 0 and the compact
+// class.  k_verify queues their items for k_verify_ladder, the small-batch
+// kernels serve them in place (verify_ladder_inline), the resident verifier
+// hands them to the ordinary path.
+__host__ __device__ inline bool key_class_queued(uint32_t wbits) {
+  return wbits == 0u || wbits >= kTeethFlag;
+}
 // Key slots >= kHostSlot carry a status the host decided for the item
 // (batch pipeline): k_verify writes the slot's low byte as the status.
 constexpr uint32_t kHostSlot = 0xFFFFFF00u;
@@ -182,6 +193,14 @@ hipError_t check_points(const uint32_t* xy, int n, uint32_t* ok, hipStream_t st)
 hipError_t point_entries(const uint32_t* xy, int n, uint32_t* out, hipStream_t st);
 hipError_t build_tables(const uint32_t* xy, int npts, int wbits, uint32_t* bpts, uint32_t* tab,
                         hipStream_t st);
+// The compact key class (teeth_dev.h): `teeth` in 2 .. 8, a table of 2^teeth
+// entries of 16 words per key (entry 0 never read) -- 256 B at 2 teeth, 1 KiB
+// at 4, 16 KiB at 8 -- verified by a comb WITH doublings, ceil(256 / teeth)
+// columns.  xy: npts validated plain affine points; tab: npts tables, one
+// after another, 64-byte aligned.  Returns when the tables are built.
+constexpr int kTeethMin = 2, kTeethMax = 8;
+size_t teeth_table_words(int teeth);
+hipError_t build_teeth_tables(const uint32_t* xy, int npts, int teeth, uint32_t* tab, hipStream_t st);
 hipError_t generator_xy(uint32_t* xy16, hipStream_t st);
 size_t ninv_workspace_words(long n);
 // One launch, one root inversion per 2,048 items (k_ninv_block, per

@@ -29,6 +29,7 @@
 
 #include "kernels.h"
 #include "ladder_dev.h"
+#include "teeth_dev.h"
 #include "modinv.h"
 #include "scalar_dev.h"
 #include "sha256.h"
@@ -279,6 +280,129 @@ __global__ void __launch_bounds__(256) k_table_fill(const uint32_t* __restrict__
       fe_mul(zi, zi, h);  // 1/Z_(j-1)
     }
   }
+}
+
+// A compact key's table (teeth_dev.h): 2^t entries of 16 words, entry v =
+// val(v) Q with val(v) = sum_j bit_j(v) 2^(j d), d = ceil(256 / t); entry 0 is
+// never read (zeroed).  One lane per key, keys [first, first + count):
+//  1. the t base points B_j = 2^(j d) Q by (t - 1) d dependent doublings,
+//     parked Jacobian and made affine with ONE inversion (Montgomery's trick
+//     over their t - 1 values of Z);
+//  2. the subset sums in ascending v, one mixed addition each: the entry
+//     without its lowest set bit (Jacobian, parked) plus that bit's base
+//     point (affine) -- a single-tooth entry is its base point, Z = 1;
+//  3. every entry made affine with ONE more inversion (Montgomery's trick
+//     over the 2^t - 1 values of Z).
+// The additions of step 2 are never degenerate: the addend is 2^(j d) Q, the
+// other operand val(v') Q with v' = v minus its lowest bit j, so val(v') has
+// its bits above j d -- the two differ, both lie in [1, 2^225), and so does
+// their sum val(v): none of val(v') -+ 2^(j d) is 0 (mod N).  No doubling
+// meets order 2 and no base point is infinity (N is prime, 2^(j d) < N).
+// (X, Y) are parked canonical in the entry's own slot; scratch holds two
+// planes of 8 words per entry and lane -- Z and the running product before
+// it -- word k of entry v at ((plane 2^t + v) 8 + k) count + lane.
+MBFT_DEV void teeth_park(uint32_t* scr, long count, long tl, long idx, const fe& a) {
+  fe c = a;
+  fe_canon(c);
+  uint32_t w[8];
+  fe_to_words(w, c);
+#pragma unroll
+  for (int k = 0; k < 8; k++) scr[(idx * 8 + k) * count + tl] = w[k];
+}
+
+MBFT_DEV void teeth_unpark(fe& a, const uint32_t* scr, long count, long tl, long idx) {
+  uint32_t w[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[k] = scr[(idx * 8 + k) * count + tl];
+  fe_from_words(a, w);
+}
+
+// scr planes [lo, hi]: entries lo .. hi (step `by`: x2 for the base points)
+// of this lane hold Z in plane 0; their (X, Y), parked in `dst`, become affine.
+template <bool POW2>
+MBFT_DEV void teeth_affine(uint32_t* dst, uint32_t* scr, long count, long tl, long ne, long lo, long hi) {
+  fe prod;
+  fe_one_mont(prod);
+#pragma unroll 1
+  for (long v = lo; v <= hi; v = POW2 ? 2 * v : v + 1) {
+    teeth_park(scr, count, tl, ne + v, prod);  // the product before v
+    fe z;
+    teeth_unpark(z, scr, count, tl, v);
+    fe_mul(prod, prod, z);
+  }
+  fe inv;
+  fe_inv(inv, prod);
+#pragma unroll 1
+  for (long v = hi; v >= lo; v = POW2 ? v / 2 : v - 1) {
+    fe pre, z, zi, z2, z3, X, Y, x, y;
+    teeth_unpark(pre, scr, count, tl, ne + v);
+    teeth_unpark(z, scr, count, tl, v);
+    fe_mul(zi, inv, pre);  // 1 / Z_v
+    fe_mul(inv, inv, z);   // 1 / (the product before v)
+    load_point(X, Y, reinterpret_cast<const uint4*>(dst + 16 * v));
+    fe_sqr(z2, zi);
+    fe_mul(z3, z2, zi);
+    fe_mul(x, X, z2);
+    fe_mul(y, Y, z3);
+    fe_canon(x);
+    fe_canon(y);
+    store_point_words(dst + 16 * v, x, y);
+  }
+}
+
+__global__ void __launch_bounds__(64) k_teeth_table(const uint32_t* __restrict__ xy, long first, long count,
+                                                    int t, uint32_t* __restrict__ scr,
+                                                    uint32_t* __restrict__ tab) {
+  const long tl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tl >= count) return;
+  const long pt = first + tl;
+  const int d = teeth_columns(t);
+  const long ne = 1L << t;
+  uint32_t* dst = tab + 16 * (pt * ne);
+  uint32_t wx[8], wy[8];
+  load_words8(wx, xy + 16 * pt);
+  load_words8(wy, xy + 16 * pt + 8);
+  jac a;
+  fe_from_words(a.X, wx);
+  fe_from_words(a.Y, wy);
+  fe_to_mont(a.X, a.X);
+  fe_to_mont(a.Y, a.Y);
+  fe_one_mont(a.Z);
+#pragma unroll
+  for (int k = 0; k < 16; k++) dst[k] = 0u;  // entry 0
+  park_xy(dst + 16, a);                       // B_0 = Q
+  teeth_park(scr, count, tl, 1, a.Z);
+  // 1. base points
+#pragma unroll 1
+  for (int j = 1; j < t; j++) {
+#pragma unroll 1
+    for (int k = 0; k < d; k++) ec_dbl(a, a);
+    park_xy(dst + 16 * (1L << j), a);
+    teeth_park(scr, count, tl, 1L << j, a.Z);
+  }
+  teeth_affine<true>(dst, scr, count, tl, ne, 2, ne / 2);
+  {
+    fe one;
+    fe_one_mont(one);
+#pragma unroll 1
+    for (int j = 1; j < t; j++) teeth_park(scr, count, tl, 1L << j, one);
+  }
+  // 2. subset sums
+#pragma unroll 1
+  for (long v = 3; v < ne; v++) {
+    const long low = v & -v;
+    if (low == v) continue;  // a base point
+    jac s;
+    load_point(s.X, s.Y, reinterpret_cast<const uint4*>(dst + 16 * (v - low)));
+    teeth_unpark(s.Z, scr, count, tl, v - low);
+    fe bx, by;
+    load_point(bx, by, reinterpret_cast<const uint4*>(dst + 16 * low));
+    ec_madd(s, s, bx, by);
+    park_xy(dst + 16 * v, s);
+    teeth_park(scr, count, tl, v, s.Z);
+  }
+  // 3. affine
+  teeth_affine<false>(dst, scr, count, tl, ne, 1, ne - 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -1396,7 +1520,9 @@ MBFT_DEV void verify_exact(const VerifyArgs& A, long i) {
 }
 
 // Item i under a table-free key (KeyDesc.wbits == 0: `tab` is the point
-// itself, one comb entry): u2 Q by the ladder (ladder_dev.h), then u1 G's
+// itself, one comb entry) or a compact key (wbits kTeethFlag | t: `tab` is
+// its 2^t entries): u2 Q by the ladder (ladder_dev.h) or by the doubling comb
+// (teeth_dev.h), then u1 G's
 // comb entries added to it one by one with complete additions -- every join
 // case (u1 G == +-u2 Q, the keys Q == +-G, u1 == 0) is exact, and the G side
 // is ~4 % of the item's work.  r, s in range and the key valid (the caller
@@ -1406,11 +1532,18 @@ MBFT_DEV void verify_ladder_item(const VerifyArgs& A, long i) {
   const KeyDesc kd = A.keys[A.slot[i]];
   uint32_t U1[8], U2[8];
   load_scalars<LANE_INV>(A, i, U1, U2);
-  fe qx, qy;
-  load_point(qx, qy, reinterpret_cast<const uint4*>(kd.tab));
   bool inf = true;
   jac j;
-  ladder_mul(j, inf, U2, qx, qy);
+  // by the key's class: a compact key's doubling comb over its own small
+  // table (teeth_dev.h), else the ladder over the point.  A wave that holds
+  // both classes runs both bodies in turn.
+  if (kd.wbits >= kTeethFlag) {
+    teeth_mul(j, inf, U2, kd.tab, (int)(kd.wbits & 0xFFu));
+  } else {
+    fe qx, qy;
+    load_point(qx, qy, reinterpret_cast<const uint4*>(kd.tab));
+    ladder_mul(j, inf, U2, qx, qy);
+  }
   comb_complete(j, inf, U1, A.tabG, A.wg);
   if (inf) {
     A.status[i] = ST_REJECT;  // (x, y) = (0, 0) -> false
@@ -1455,7 +1588,7 @@ MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf,
   // second compacted queue, which k_verify_ladder serves (one atomic per
   // wave) and whose status is that kernel's to write (kNoStatus here)
   constexpr uint8_t kNoStatus = 0xFF;
-  const bool tfree = key_ok && kd.wbits == 0u;
+  const bool tfree = key_ok && key_class_queued(kd.wbits);
   const bool queued = tfree && in_batch && range_ok && (A.host_status & kArgTableFree);
   const uint8_t dead_status =
       queued ? kNoStatus
@@ -1589,7 +1722,7 @@ MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, 
       key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
   // a table-free key (window 0) takes no part in the comb: its even lane
   // runs the ladder at the end
-  const bool tfree = key_ok && kd.wbits == 0u;
+  const bool tfree = key_ok && key_class_queued(kd.wbits);
   const bool live = in_batch && key_ok && range_ok && !tfree;
   uint32_t U1[8], U2[8];
 #pragma unroll
@@ -1736,7 +1869,7 @@ MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uin
       key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
   // a table-free key (window 0) takes no part in the comb: its even lane
   // runs the ladder at the end
-  const bool tfree = key_ok && kd.wbits == 0u;
+  const bool tfree = key_ok && key_class_queued(kd.wbits);
   const bool live = in_batch && key_ok && range_ok && !tfree;
   uint32_t U1[8], U2[8];
 #pragma unroll
@@ -2098,7 +2231,7 @@ MBFT_DEV void split_item(const VerifyArgs& A, long i, uint32_t (&part)[NP][4 * N
   const bool range_ok = !words_is_zero(rw) && words_lt(rw, kNw) && !words_is_zero(sw) && words_lt(sw, kNw);
   KeyDesc kd{A.tabG, (uint32_t)A.wg, 0u};
   if (slot < A.nslots) kd = A.keys[slot];
-  const bool tfree = slot < A.nslots && kd.valid && kd.wbits == 0u;
+  const bool tfree = slot < A.nslots && kd.valid && key_class_queued(kd.wbits);
   const bool key_ok = slot < A.nslots && kd.valid && (TFREE || !tfree);
   if (!(key_ok && range_ok) || tfree) {  // block-uniform: the whole workgroup returns
     // the status last, after every wave has read the inputs: the host may
@@ -3095,6 +3228,32 @@ hipError_t build_tables(const uint32_t* xy, int npts, int wbits, uint32_t* bpts,
     const long cnt = total - first < chunk ? total - first : chunk;
     hipLaunchKernelGGL(k_table_fill, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st,
                        bpts, npts, wbits, first, cnt, scratch, tab);
+    e = hipGetLastError();
+    if (e != hipSuccess) break;
+  }
+  // the launches read the scratch until they finish
+  const hipError_t es = hipStreamSynchronize(st);
+  const hipError_t ef = hipFree(scratch);
+  return e != hipSuccess ? e : (es != hipSuccess ? es : ef);
+}
+
+size_t teeth_table_words(int teeth) { return ((size_t)1 << teeth) * 16u; }
+
+hipError_t build_teeth_tables(const uint32_t* xy, int npts, int teeth, uint32_t* tab, hipStream_t st) {
+  if (npts <= 0) return hipSuccess;
+  if (teeth < kTeethMin || teeth > kTeethMax) return hipErrorInvalidValue;
+  // one lane per key, in launches whose scratch (as large as their tables:
+  // two planes of 8 words per entry) stays within 64 MiB
+  const size_t per_key = teeth_table_words(teeth) * 4;
+  long chunk = (long)(((size_t)64 << 20) / per_key);
+  if (chunk > npts) chunk = npts;
+  uint32_t* scratch = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&scratch), (size_t)chunk * per_key);
+  if (e != hipSuccess) return e;
+  for (long first = 0; first < npts; first += chunk) {
+    const long cnt = npts - first < chunk ? npts - first : chunk;
+    hipLaunchKernelGGL(k_teeth_table, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st, xy, first, cnt,
+                       teeth, scratch, tab);
     e = hipGetLastError();
     if (e != hipSuccess) break;
   }

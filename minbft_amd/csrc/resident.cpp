@@ -509,7 +509,8 @@ int resident_call(mbft_ctx* c, const mbft_item& it, uint8_t* st) {
     if (key >= c->keydesc.size()) return fail(c, MBFT_ERR_STATE, "resident verifier: key slot");
     // a table-free key (window 0) is the ladder's, which the mailbox kernel
     // does not carry: the ordinary single-call path serves it
-    if (c->keydesc[key].valid && c->keydesc[key].wbits == 0u) return kNoResident;
+    // (a compact key, teeth_dev.h, likewise)
+    if (c->keydesc[key].valid && mbft::key_class_queued(c->keydesc[key].wbits)) return kNoResident;
 #ifdef MBFT_SRV_TIMING
     const double tt1 = now_ms();
 #endif
@@ -582,7 +583,7 @@ int resident_check(mbft_ctx* c, const mbft_item* items, size_t n, uint8_t* gst,
     } else {
       if (key[i] >= c->keydesc.size()) return fail(c, MBFT_ERR_STATE, "resident verifier: key slot");
       // (a table-free key: the whole check takes the ordinary path, as above)
-      if (c->keydesc[key[i]].valid && c->keydesc[key[i]].wbits == 0u) return kNoResident;
+      if (c->keydesc[key[i]].valid && mbft::key_class_queued(c->keydesc[key[i]].wbits)) return kNoResident;
       gpu[m++] = i;
     }
   }
