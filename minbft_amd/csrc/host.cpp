@@ -418,13 +418,17 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
   HIPCHK(c, c->ws[k].ensure(wwords * 4));
   HIPCHK(c, c->winv[k].ensure((size_t)9 * n * 4));
   // Small batches: no batched s^-1 chain (five dependent launches, ~180 us
-  // of latency); k_verify_pairs inverts s per lane (divsteps, modinv.h).
+  // of latency); the small-batch forms invert s themselves (verify_plan.h).
   // Env MBFT_LANE_INV_MAX (default 4096 items; 0 disables).
   static const size_t lane_inv_max = mbft::env_size("MBFT_LANE_INV_MAX", 4096);
-  // d_count: n is an upper bound, the count is on the device -- the small-batch
-  // kernels, which read it (no batched chain: it is sized by n on the host)
-  const bool small = n <= lane_inv_max || d_count;
-  HIPCHK(c, c->slowq[k].ensure(mbft_launch::verify_words((long)n, small) * 4));
+  // The batch's form, decided once: it sizes slowq[k] (the spill planes of
+  // the grid that runs), names the s^-1 to run here and goes to the launcher.
+  const mbft::InvSource src = mbft::verify_inv_source((long)n, lane_inv_max, d_winv != nullptr, d_count != nullptr);
+  const mbft::VerifyPlan plan =
+      mbft::verify_plan((long)n, src, d_count != nullptr, /*has_planes_ws=*/!d_winv,
+                        tb->split_max < 0 ? mbft_launch::split_max_env() : tb->split_max,
+                        tb->small_inv < 0 ? 2 : tb->small_inv);
+  HIPCHK(c, c->slowq[k].ensure(mbft::verify_slowq_words((long)n, plan) * 4));
   mbft_ctx::Ev ev{};
   if (c->prof) {
     HIPCHK(c, hipEventCreate(&ev.a));
@@ -434,18 +438,17 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
     ev.n = n;
   }
   // Every path ends the same way on the caller's stream: the verify over w
-  // planes `winv` (null: the small-batch forms, which alone read split_max,
-  // d_count, the planes workspace and small_inv), then ev_done[k].  Profiling
-  // brackets it with ev.c and ev.d; ev.a and ev.b (the s^-1 span) are each
-  // path's own.
-  auto verify_and_mark_done = [&](const uint32_t* winv, bool queue_zeroed) -> int {
+  // planes `winv` (null: the forms that invert s themselves), then
+  // ev_done[k].  Profiling brackets it with ev.c and ev.d; ev.a and ev.b (the
+  // s^-1 span) are each path's own.
+  auto verify_and_mark_done = [&](const uint32_t* winv) -> int {
     if (c->prof) HIPCHK(c, hipEventRecord(ev.c, st));
-    HIPCHK(c, mbft_launch::verify(d_e, d_r, d_s, d_slot, winv, tb->d_tabG, tb->g_wbits,
-                                  tb->d_keys.as<mbft::KeyDesc>(), (uint32_t)tb->slots.size(),
-                                  (long)n, d_status, c->slowq[k].as<uint32_t>(), st, host_status,
-                                  queue_zeroed, tb->split_max, /*split_winv=*/d_winv != nullptr,
-                                  d_count, /*planes_ws=*/d_winv ? nullptr : c->winv[k].as<uint32_t>(),
-                                  tb->small_inv, /*table_free=*/tb->tfree_keys != 0));
+    const mbft_launch::VerifyBatch vb{d_e, d_r, d_s, d_slot, (long)n, d_status, c->slowq[k].as<uint32_t>(), winv,
+                                      /*planes_ws=*/d_winv ? nullptr : c->winv[k].as<uint32_t>(), d_count,
+                                      host_status};
+    const mbft_launch::VerifyTables vt{tb->d_tabG, tb->g_wbits, tb->d_keys.as<mbft::KeyDesc>(),
+                                       (uint32_t)tb->slots.size(), tb->tfree_keys != 0};
+    HIPCHK(c, mbft_launch::verify(vb, vt, plan, st));
     HIPCHK(c, hipEventRecord(c->ev_done[k], st));
     if (c->prof) {
       HIPCHK(c, hipEventRecord(ev.d, st));
@@ -453,13 +456,13 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
     }
     return MBFT_OK;
   };
-  if (small || d_winv) {
+  if (src != mbft::InvSource::kBatch) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // slowq[k] reuse
     if (c->prof) {
       HIPCHK(c, hipEventRecord(ev.a, st));
       HIPCHK(c, hipEventRecord(ev.b, st));
     }
-    return verify_and_mark_done(d_winv, /*queue_zeroed=*/false);
+    return verify_and_mark_done(d_winv);
   }
   // The batched s^-1 has three forms:
   //  1. every earlier batch of this engine has finished (one batch at a time:
@@ -498,14 +501,14 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
     if (c->prof) HIPCHK(c, hipEventRecord(ev.a, st));
     HIPCHK(c, mbft_launch::batch_inverse_s_local(d_s, (long)n, winv, qlen, st));
     if (c->prof) HIPCHK(c, hipEventRecord(ev.b, st));
-    return verify_and_mark_done(winv, /*queue_zeroed=*/true);
+    return verify_and_mark_done(winv);
   }
   if (!levels) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // winv[k] / slowq[k] reuse
     if (c->prof) HIPCHK(c, hipEventRecord(ev.a, st));
     HIPCHK(c, mbft_launch::batch_inverse_s_pipelined(d_s, (long)n, winv, qlen, st));
     if (c->prof) HIPCHK(c, hipEventRecord(ev.b, st));
-    return verify_and_mark_done(winv, /*queue_zeroed=*/true);
+    return verify_and_mark_done(winv);
   }
   // inputs ready on the caller's stream; buffer k free once the verify that
   // last read it (two calls ago) has finished
@@ -521,7 +524,7 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
   // slowq[k]: free once the verify that last used it has finished (it may
   // have run on another stream)
   HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));
-  return verify_and_mark_done(winv, /*queue_zeroed=*/true);
+  return verify_and_mark_done(winv);
 }
 
 // Host buffers in, host status out, on ONE engine.

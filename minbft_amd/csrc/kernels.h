@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "verify_plan.h"
+
 namespace mbft {
 // Per key slot, read by k_verify (16 B): the key's comb table, its window and
 // whether the key passed validation.  A table-free key (window 0): tab is the
@@ -220,21 +222,30 @@ hipError_t batch_inverse_s(const uint8_t* s, long n, uint32_t* ws, uint32_t* win
 hipError_t sign(const uint8_t* priv, const uint32_t* key_idx, const uint8_t* e, const uint8_t* k_in,
                 long n, const uint32_t* tabG, int wg, uint8_t* r_out, uint8_t* s_out,
                 hipStream_t st);
-// words of the `slowq` buffer verify() needs for n items (exact-path queue,
-// the table-free queue, their lengths, the rare comb steps' scratch; `pairs`:
-// the small-batch kernels, up to four threads per item)
-size_t verify_words(long n, bool pairs = false);
-size_t verify_scratch_offset(long n);
-hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const uint32_t* slot,
-                  const uint32_t* winv, const uint32_t* tabG, int wg, const KeyDesc* keys,
-                  uint32_t nslots, long n, uint8_t* status, uint32_t* slowq, hipStream_t st,
-                  bool host_status = false, bool queue_zeroed = false, long split_max = -1,
-                  bool split_winv = false, const uint32_t* ndev = nullptr,
-                  uint32_t* planes_ws = nullptr, int small_form = -1, bool table_free = false);
-// (planes_ws: 9 n words the small-batch forms may use for the batched s^-1
-// planes; small_form: their form, mbft_set_small_batch_inverse's modes;
-// table_free: some key slot has window 0 -- k_verify queues such items and
-// k_verify_ladder follows it; the small-batch forms serve them in place)
+// One batch for verify(): n items in device memory and the buffers they use.
+struct VerifyBatch {
+  const uint8_t *e, *r, *s;  // n x 32 B big-endian each
+  const uint32_t* slot;     // n key slots
+  long n;
+  uint8_t* status;
+  uint32_t* slowq;          // verify_slowq_words(n, plan) words (verify_plan.h)
+  const uint32_t* winv;     // the s^-1 R planes the plan's source names: 9 planes of n, the host's
+                            // followed by u1, u2 (16 words an item, batch.cpp host_winv_u); or null
+  uint32_t* planes_ws;      // 9 n words for the forms that run k_ninv_local<1> first, or null
+  const uint32_t* ndev;     // optional: the item count on the device, <= n
+  bool host_status;         // slots >= kHostSlot carry the host's status
+};
+// The tables a batch is verified under.
+struct VerifyTables {
+  const uint32_t* tabG;     // generator comb table, window wg
+  int wg;
+  const KeyDesc* keys;
+  uint32_t nslots;
+  bool table_free;          // some key is of a class the comb does not serve (key_class_queued)
+};
+// MBFT_SPLIT_MAX (default 256; 0 disables the split form), read once.
+long split_max_env();
+hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const mbft::VerifyPlan& plan, hipStream_t st);
 // The resident verifier: one 256-thread workgroup per mailbox slot, or two
 // (`two`: one per scalar, each on its own CU).
 hipError_t verify_server(const mbft::ServerArgs& a, int servers, bool two, hipStream_t st);

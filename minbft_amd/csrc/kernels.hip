@@ -897,10 +897,10 @@ struct VerifyArgs {
 constexpr uint32_t kArgHostStatus = 1u, kArgTableFree = 2u;
 
 // The table-free items' queue (k_verify -> k_verify_ladder) inside the
-// `slowq` buffer (mbft_launch::verify_words): its length right after the
-// exact-path queue's, its n entries from the next 64-word boundary.  Derived
-// from slowq / slown, so the kernels' argument block is what it was.
-__host__ __device__ inline size_t ladder_queue_offset(long n) { return ((size_t)n + 2 + 63) & ~(size_t)63; }
+// `slowq` buffer (verify_plan.h): its length right after the exact-path
+// queue's, its n entries from ladder_queue_offset.  Derived from slowq /
+// slown, so the kernels' argument block is what it was.
+static_assert(kSpillPlanes == 4 * NL, "Spill: X, Y, ZZ, ZZZ of NL limbs");
 MBFT_DEV uint32_t* ladder_count(const VerifyArgs& A) { return A.slown + 1; }
 MBFT_DEV uint32_t* ladder_queue(const VerifyArgs& A) { return A.slowq + ladder_queue_offset(A.n); }
 
@@ -1235,203 +1235,6 @@ MBFT_DEV bool comb_verify_fast(chud& acc, uint32_t (&U1)[8], uint32_t (&U2)[8],
   return inf;
 }
 
-constexpr unsigned kWaitVm4 = 0x0F74;  // s_waitcnt vmcnt(4): all but the youngest gather (4 loads)
-
-// This lane's entry from a cooperative gather slot whose LDS-DMA the caller
-// has waited for.  The LDS reads are inline asm (with their own lgkmcnt(0)):
-// the compiler tracks LDS-DMA writes by LDS object and, unable to tell two
-// slots of one array apart, would turn the caller's vmcnt(4) into vmcnt(0),
-// i.e. wait for the younger gather too.  The outputs are early-clobber: a
-// destination sharing the address VGPR would let a fast first read land
-// before a later read of the block has sent its address.
-MBFT_DEV void slot_read(fe& px, fe& py, const uint4* buf) {
-  const uint32_t a = (uint32_t)(uintptr_t)(buf + 4 * __lane_id());  // low half of a flat LDS address = the offset
-  uint4 c0, c1, c2, c3;
-  asm volatile(
-      "ds_read_b128 %0, %4\n\t"
-      "ds_read_b128 %1, %4 offset:16\n\t"
-      "ds_read_b128 %2, %4 offset:32\n\t"
-      "ds_read_b128 %3, %4 offset:48\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3)
-      : "v"(a)
-      : "memory");
-  uint32_t wx[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-  uint32_t wy[8] = {c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
-  fe_from_words(px, wx);
-  fe_from_words(py, wy);
-}
-
-// The issue side of comb_verify_fast2: the stream of entries after the first
-// two G windows -- G windows gk .. SG-1, then Q windows qk .. SQ-1 -- with
-// each scalar's recoding carry; next() gathers the next entry into `buf`
-// (its digit's sign and zero flag out).
-struct CombStream {
-  const uint32_t* tabG;
-  const uint32_t* tabQ;
-  int wg, wq, SG, SQ, gk, qk;
-  uint32_t carry, qcarry;
-};
-
-MBFT_DEV void comb_stream_next(CombStream& cs, uint32_t (&U1)[8], uint32_t (&U2)[8], uint4* buf, bool& n,
-                               bool& z) {
-  const uint4* e;
-  if (cs.gk < cs.SG) {  // wave-uniform
-    const uint32_t idx = comb_digit(U1[0], cs.carry, cs.wg, cs.gk + 1 >= cs.SG, n, z);
-    e = comb_entry(cs.tabG, cs.wg, cs.gk, idx);
-    shr_words(U1, cs.wg);
-    cs.gk++;
-  } else {
-    const uint32_t idx = comb_digit(U2[0], cs.qcarry, cs.wq, cs.qk + 1 >= cs.SQ, n, z);
-    e = comb_entry(cs.tabQ, cs.wq, cs.qk, idx);
-    shr_words(U2, cs.wq);
-    cs.qk++;
-  }
-  gather_issue<true>(e, buf);
-}
-
-// One step of comb_verify_fast2: the entry of step k (slot A for even k, its
-// digit flags na / za, else B), the slot refilled at once with step k + 2,
-// then the mixed addition with comb_step's rare branches.  T: the steps.
-template <bool LAST>
-MBFT_DEV void comb_step2(chud& acc, bool& inf, bool& yneg, bool& na, bool& za, bool& nb, bool& zb,
-                         uint32_t (&U1)[8], uint32_t (&U2)[8], CombStream& cs, int k, int T, uint4* bufA,
-                         uint4* bufB, const Spill& sp, bool live, StepClock& sc) {
-  const bool odd = (k & 1) != 0;
-  uint4* buf = odd ? bufB : bufA;
-  fe px, py;
-#ifdef MBFT_STEP_TIMING
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#endif
-  if (k + 1 < T)  // wave-uniform: the other slot's gather stays in flight
-    __builtin_amdgcn_s_waitcnt(kWaitVm4);
-  else
-    __builtin_amdgcn_s_waitcnt(kWaitVm0);
-#ifdef MBFT_STEP_TIMING
-  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-#endif
-  slot_read(px, py, buf);
-#ifdef MBFT_STEP_TIMING
-  const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-#endif
-  const bool neg = odd ? nb : na, zero = odd ? zb : za;
-  if (k + 2 < T) {
-    bool n2, z2;
-    comb_stream_next(cs, U1, U2, buf, n2, z2);
-    if (odd) {
-      nb = n2;
-      zb = z2;
-    } else {
-      na = n2;
-      za = z2;
-    }
-  }
-#ifdef MBFT_STEP_TIMING
-  const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-#endif
-  // dead lanes (zero scalars, results discarded) never count as rare
-  const bool rare = __ballot(live && (zero || inf)) != 0;
-  if (rare && live) {
-    if (zero) {
-      sp.put(0, acc.X);
-      sp.put(1, acc.Y);
-      sp.put(2, acc.ZZ);
-      sp.put(3, acc.ZZZ);
-    } else if (inf) {
-      sp.put(0, px);
-      sp.put(1, py);
-    }
-  }
-  ec_madd_chud<true, LAST>(acc, acc, px, py, yneg != neg);  // Y takes the digit's sign (ecc.h)
-  const bool yold = yneg;
-  yneg = neg;
-  if (rare && live) {
-    if (zero) {  // d = 0: nothing added
-      sp.get(0, acc.X);
-      sp.get(1, acc.Y);
-      sp.get(2, acc.ZZ);
-      sp.get(3, acc.ZZZ);
-      yneg = yold;
-    } else if (inf) {  // infinity + entry = entry (Z = 1); acc.Y holds t y2
-      sp.get(0, acc.X);
-      sp.get(1, acc.Y);
-      fe_one_mont(acc.ZZ);
-      fe_one_mont(acc.ZZZ);
-      yneg = neg;
-      inf = false;
-    }
-  }
-#ifdef MBFT_STEP_TIMING
-  const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-  sc.s[0] += t1 - t0;
-  sc.s[1] += t2 - t1;
-  sc.s[2] += t3 - t2;
-  sc.s[3] += t4 - t3;
-  sc.steps += 1;
-#else
-  (void)sc;
-#endif
-}
-
-// comb_verify_fast<true> with TWO gathers in flight (k_verify, every lane's
-// key window the same): each wave has two LDS slots; the entry of step k is
-// read from its slot (waiting only for that gather: vmcnt(4) leaves the
-// younger one in flight), the slot is refilled at once with the entry of step
-// k + 2, then the mixed addition runs -- a gather has two additions to land
-// instead of one (at one wave per SIMD the one-step prefetch left 17 % of
-// each step waiting for it, tools/step_timing.py).  The G windows 2 .. SG-1
-// and the Q windows 0 .. SQ-1 are one stream of steps, so the first Q entries
-// are in flight during the last G additions, and the first two G entries are
-// fetched at once.  Same additions, same rare branches, same results as
-// comb_verify_fast.
-MBFT_DEV bool comb_verify_fast2(chud& acc, uint32_t (&U1)[8], uint32_t (&U2)[8], const uint32_t* tabG,
-                                int wg, const uint32_t* tabQ, int wq, uint4* bufA, uint4* bufB,
-                                const Spill& sp, bool live, StepClock& sc) {
-  CombStream cs{tabG, tabQ, wg, wq, (256 + wg - 1) / wg, (256 + wq - 1) / wq, 2, 0, 0u, 0u};
-  const int T = cs.SG - 2 + cs.SQ;  // mixed additions
-  bool neg0, zero0, neg1, zero1;
-  const uint32_t i0 = comb_digit(U1[0], cs.carry, wg, false, neg0, zero0);
-  shr_words(U1, wg);
-  const uint32_t i1 = comb_digit(U1[0], cs.carry, wg, false, neg1, zero1);
-  shr_words(U1, wg);
-  gather_issue<true>(comb_entry(tabG, wg, 0, i0), bufA);
-  gather_issue<true>(comb_entry(tabG, wg, 1, i1), bufB);
-  bool na, za, nb, zb;  // the digit flags of the entries in slots A and B
-  {
-    // the first two G windows: affine + affine.  acc.Y holds +-Y (only X and
-    // Z are read afterwards): a negative first digit just starts the lane
-    // with Y negated.
-    fe x0, y0, x1, y1;
-    __builtin_amdgcn_s_waitcnt(kWaitVm4);
-    slot_read(x0, y0, bufA);
-    comb_stream_next(cs, U1, U2, bufA, na, za);
-    __builtin_amdgcn_s_waitcnt(kWaitVm4);
-    slot_read(x1, y1, bufB);
-    comb_stream_next(cs, U1, U2, bufB, nb, zb);
-    ec_add_affine_chud(acc, x0, y0, x1, y1, neg0 != neg1);
-  }
-  bool yneg = !neg0, inf = false;
-  if (__ballot(live && (zero0 || zero1)) != 0) {
-    // a zero digit among the first two: the sum is the other entry (Z = 1,
-    // reloaded per lane), or infinity if both are zero
-    if (zero0 && zero1) {
-      inf = true;
-    } else if (zero0 || zero1) {
-      load_point(acc.X, acc.Y, comb_entry(tabG, wg, zero0 ? 1 : 0, zero0 ? i1 : i0));
-      fe_one_mont(acc.ZZ);
-      fe_one_mont(acc.ZZZ);
-      yneg = zero0 ? neg1 : neg0;
-    }
-  }
-#pragma unroll 1
-  for (int k = 0; k < T - 1; k++)
-    comb_step2<false>(acc, inf, yneg, na, za, nb, zb, U1, U2, cs, k, T, bufA, bufB, sp, live, sc);
-  // the chain's last addition: X and ZZ only (the x-check)
-  comb_step2<true>(acc, inf, yneg, na, za, nb, zb, U1, U2, cs, T - 1, T, bufA, bufB, sp, live, sc);
-  fe_norm_lazy(acc.ZZ);
-  return inf;
-}
-
 // Same sum with exact handling of doubling / opposite points / infinity.
 MBFT_DEV void comb_complete(jac& acc, bool& inf, uint32_t (&U)[8], const uint32_t* tab, int W) {
   const int S = (256 + W - 1) / W;
@@ -1497,8 +1300,21 @@ MBFT_DEV void verify_finish(const VerifyArgs& A, long i, const fe& X, const fe& 
   A.status[i] = x_matches_r(X, ZZ, rw) ? ST_ACCEPT : ST_REJECT;
 }
 
+// The ending of the paths that sum with complete additions (verify_exact,
+// verify_ladder_item): a final infinity rejects, as Go's (0, 0) does, else the
+// accept test on X and ZZ = Z^2.
+MBFT_DEV void verify_finish_jac(const VerifyArgs& A, long i, const jac& j, bool inf) {
+  if (inf) {
+    A.status[i] = ST_REJECT;  // (x, y) = (0, 0) -> false
+    return;
+  }
+  fe ZZ;
+  fe_sqr(ZZ, j.Z);
+  verify_finish(A, i, j.X, ZZ);
+}
+
 // The exact path for item i: both phases recomputed with complete additions
-// (doubling, infinity).  A final infinity rejects, as Go's (0, 0) does.
+// (doubling, infinity).
 MBFT_DEV void verify_exact(const VerifyArgs& A, long i) {
   KeyDesc kd = A.keys[A.slot[i]];
   uint32_t U1[8], U2[8];
@@ -1510,13 +1326,7 @@ MBFT_DEV void verify_exact(const VerifyArgs& A, long i) {
   jac j;
   comb_complete(j, inf, U1, A.tabG, A.wg);
   comb_complete(j, inf, U2, kd.tab, (int)kd.wbits);
-  if (inf) {
-    A.status[i] = ST_REJECT;  // (x, y) = (0, 0) -> false
-    return;
-  }
-  fe ZZ;
-  fe_sqr(ZZ, j.Z);
-  verify_finish(A, i, j.X, ZZ);
+  verify_finish_jac(A, i, j, inf);
 }
 
 // Item i under a table-free key (KeyDesc.wbits == 0: `tab` is the point
@@ -1526,7 +1336,7 @@ MBFT_DEV void verify_exact(const VerifyArgs& A, long i) {
 // comb entries added to it one by one with complete additions -- every join
 // case (u1 G == +-u2 Q, the keys Q == +-G, u1 == 0) is exact, and the G side
 // is ~4 % of the item's work.  r, s in range and the key valid (the caller
-// checked).  A final infinity rejects, as Go's (0, 0) does.
+// checked).
 template <bool LANE_INV>
 MBFT_DEV void verify_ladder_item(const VerifyArgs& A, long i) {
   const KeyDesc kd = A.keys[A.slot[i]];
@@ -1545,13 +1355,7 @@ MBFT_DEV void verify_ladder_item(const VerifyArgs& A, long i) {
     ladder_mul(j, inf, U2, qx, qy);
   }
   comb_complete(j, inf, U1, A.tabG, A.wg);
-  if (inf) {
-    A.status[i] = ST_REJECT;  // (x, y) = (0, 0) -> false
-    return;
-  }
-  fe ZZ;
-  fe_sqr(ZZ, j.Z);
-  verify_finish(A, i, j.X, ZZ);
+  verify_finish_jac(A, i, j, inf);
 }
 
 // (the small-batch forms: s^-1 from the planes where the batch has them)
@@ -1562,11 +1366,62 @@ MBFT_DEV void verify_ladder_inline(const VerifyArgs& A, long i) {
     verify_ladder_item<true>(A, i);
 }
 
+// What every form settles about an item before any curve arithmetic.
+// crypto/ecdsa.Verify rejects r <= 0 || s <= 0 || r >= N || s >= N.  An
+// unknown slot or a key that failed validation is BAD_KEY, except that slots
+// >= kHostSlot carry a status the host decided (batch pipeline), written as
+// is, so the statuses the host reads back are final.  A key of a class the
+// comb does not serve (key_class_queued) is `tfree`: never live; the form runs
+// the ladder for it (verify_ladder_inline) or, in k_verify, queues it.
+// An item that is not `live` is dead: past the end of the batch (in_batch
+// false: the caller passes item 0), bad key, bad range or tfree.  Dead lanes
+// still run their form's comb -- the cooperative gather needs all 64 lanes,
+// the lane pairs and quads their shuffles -- on zero scalars over a valid
+// table (kd defaults to the generator's) and write only dead_status: k_verify
+// BEFORE the comb, so that nothing of a dead lane stays live across it.
+struct Admission {
+  uint32_t rw[8], sw[8];
+  uint32_t slot;
+  KeyDesc kd;
+  bool range_ok, key_ok, tfree, live;
+  uint8_t dead_status;
+};
+
+MBFT_DEV void admit(Admission& a, const VerifyArgs& A, long ii, bool in_batch) {
+  load_be256(a.rw, A.r + 32 * ii);
+  load_be256(a.sw, A.s + 32 * ii);
+  a.slot = A.slot[ii];
+  a.range_ok = !words_is_zero(a.rw) && words_lt(a.rw, kNw) &&
+               !words_is_zero(a.sw) && words_lt(a.sw, kNw);
+  a.kd = KeyDesc{A.tabG, (uint32_t)A.wg, 0u};
+  if (a.slot < A.nslots) a.kd = A.keys[a.slot];
+  a.key_ok = a.slot < A.nslots && a.kd.valid;
+  a.dead_status = a.key_ok ? ST_REJECT
+                           : ((A.host_status & kArgHostStatus) && a.slot >= kHostSlot ? (uint8_t)a.slot : ST_BAD_KEY);
+  a.tfree = a.key_ok && key_class_queued(a.kd.wbits);
+  a.live = in_batch && a.key_ok && a.range_ok && !a.tfree;
+}
+
+// Item index i appended to a compacted queue by every lane that calls this
+// together: one atomic per wave.
+MBFT_DEV void queue_push(uint32_t* count, uint32_t* queue, long i) {
+  const uint64_t qm = __ballot(true);
+  const int nq = __popcll(qm);
+  const int rank = __popcll(qm & ((1ull << __lane_id()) - 1ull));
+  const int leader = __ffsll((unsigned long long)qm) - 1;
+  uint32_t base = 0;
+  if (__lane_id() == leader) base = atomicAdd(count, (uint32_t)nq);
+  base = __shfl(base, leader);
+  queue[base + rank] = (uint32_t)i;
+}
+
 // One item per thread.  Every lane of the wave runs the comb loop (the
 // cooperative gather needs all 64): lanes past the end of the batch, with an
 // unknown / invalid key, or with r or s out of range are "dead" -- they run
 // the loop on zero scalars over a valid table and write only their status.
-MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf, uint4* buf2) {
+// (admit's rules, open-coded: through the helper k_verify's register
+// allocation moved and the large batches measured 0.7 % slower)
+MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf) {
 #ifdef MBFT_STEP_TIMING
   const unsigned long long tv0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1595,14 +1450,7 @@ MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf,
              : key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
   const bool live = in_batch && key_ok && range_ok && !tfree;
   if (queued) {
-    const uint64_t qm = __ballot(true);
-    const int nq = __popcll(qm);
-    const int rank = __popcll(qm & ((1ull << __lane_id()) - 1ull));
-    const int leader = __ffsll((unsigned long long)qm) - 1;
-    uint32_t base = 0;
-    if (__lane_id() == leader) base = atomicAdd(ladder_count(A), (uint32_t)nq);
-    base = __shfl(base, leader);
-    ladder_queue(A)[base + rank] = (uint32_t)i;
+    queue_push(ladder_count(A), ladder_queue(A), i);
   }
 
   // w = s^-1 (Montgomery form), u1 = e w, u2 = r w (plain, canonical < N).
@@ -1639,19 +1487,8 @@ MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf,
 #ifdef MBFT_STEP_TIMING
   const unsigned long long tc0 = __builtin_amdgcn_s_memtime(), rc0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  // The two-step-ahead gathers (comb_verify_fast2) measured no faster than
-  // the one-step prefetch (round 5, same box: isolated 1.072-1.094 against
-  // 1.063-1.065 ms, C2 1,015 against 1,014-1,021 M/s): the wait they remove is
-  // not what leaves the SIMD idle.  Kept for A/B builds.
-  static constexpr bool kTwoDeep =
-#ifdef MBFT_TWO_DEEP_GATHER
-      true;
-#else
-      false;
-#endif
-  const bool inf = !quni    ? comb_verify_fast<false>(acc, U1, U2, A.tabG, A.wg, tq, wq, buf, sp, live, sc)
-                   : kTwoDeep ? comb_verify_fast2(acc, U1, U2, A.tabG, A.wg, tq, wq, buf, buf2, sp, live, sc)
-                              : comb_verify_fast<true>(acc, U1, U2, A.tabG, A.wg, tq, wq, buf, sp, live, sc);
+  const bool inf = !quni ? comb_verify_fast<false>(acc, U1, U2, A.tabG, A.wg, tq, wq, buf, sp, live, sc)
+                         : comb_verify_fast<true>(acc, U1, U2, A.tabG, A.wg, tq, wq, buf, sp, live, sc);
 #ifdef MBFT_STEP_TIMING
   const unsigned long long tc1 = __builtin_amdgcn_s_memtime(), rc1 = __builtin_amdgcn_s_memrealtime();
   if (__lane_id() == 0) {
@@ -1683,17 +1520,82 @@ MBFT_DEV void verify_one(const VerifyArgs& A, long i, bool in_batch, uint4* buf,
     // k_verify_slow over a compacted queue, so that a crafted item costs its
     // own exact recomputation only -- not a stall of the 63 other lanes of
     // its wave.  One atomic per wave.
-    const uint64_t qm = __ballot(true);
-    const int nq = __popcll(qm);
-    const int rank = __popcll(qm & ((1ull << __lane_id()) - 1ull));
-    const int leader = __ffsll((unsigned long long)qm) - 1;
-    uint32_t base = 0;
-    if (__lane_id() == leader) base = atomicAdd(A.slown, (uint32_t)nq);
-    base = __shfl(base, leader);
-    A.slowq[base + rank] = (uint32_t)i;
+    queue_push(A.slown, A.slowq, i);
     return;
   }
   verify_finish(A, i, acc.X, acc.ZZ);
+}
+
+// G's first two windows on ONE lane (per-lane loads; comb_verify_fast gathers
+// its own cooperatively): affine + affine, zero digits exact.  Leaves U and
+// carry at window 2.
+MBFT_DEV void comb_start_affine(chud& acc, bool& inf, bool& yneg, uint32_t (&U)[8], uint32_t& carry,
+                                const uint32_t* tab, int W) {
+  bool neg0, zero0, neg1, zero1;
+  const uint32_t i0 = comb_digit(U[0], carry, W, false, neg0, zero0);
+  shr_words(U, W);
+  const uint32_t i1 = comb_digit(U[0], carry, W, false, neg1, zero1);
+  shr_words(U, W);
+  fe x0, y0, x1, y1;
+  load_point(x0, y0, comb_entry(tab, W, 0, i0));
+  load_point(x1, y1, comb_entry(tab, W, 1, i1));
+  ec_add_affine_chud(acc, x0, y0, x1, y1, neg0 != neg1);
+  yneg = !neg0;
+  inf = zero0 && zero1;
+  if (zero0 != zero1) {
+    acc.X = zero0 ? x1 : x0;
+    acc.Y = zero0 ? y1 : y0;
+    fe_one_mont(acc.ZZ);
+    fe_one_mont(acc.ZZZ);
+    yneg = zero0 ? neg1 : neg0;
+  }
+}
+
+// o = the sum held by the lane at distance `mask` (lane id xor mask)
+MBFT_DEV void chud_shfl_xor(chud& o, const chud& a, int mask) {
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    o.X.v[k] = __shfl_xor(a.X.v[k], mask);
+    o.Y.v[k] = __shfl_xor(a.Y.v[k], mask);
+    o.ZZ.v[k] = __shfl_xor(a.ZZ.v[k], mask);
+    o.ZZZ.v[k] = __shfl_xor(a.ZZZ.v[k], mask);
+  }
+}
+
+// The ending of a dead item on its first lane, after the comb: a tfree key's
+// item by the ladder, else the status admit chose.
+MBFT_DEV void verify_dead(const VerifyArgs& A, long i, bool in_batch, const Admission& ad) {
+  if (in_batch && ad.tfree && ad.range_ok)
+    verify_ladder_inline(A, i);
+  else if (in_batch)
+    A.status[i] = ad.dead_status;
+}
+
+// The ending of a live item: u1 G (acc, inf) and u2 Q (o, oinf) joined by the
+// x-only addition, then the accept test.  same_sign: ecc.h's Y convention
+// agrees between the two.  u1 G == +-u2 Q (the join fails, or leaves ZZ == 0)
+// takes the exact path.
+MBFT_DEV void verify_join(const VerifyArgs& A, long i, const chud& acc, bool inf, const chud& o, bool oinf,
+                          bool same_sign) {
+  fe X, ZZ;
+  if (inf && oinf) {
+    A.status[i] = ST_REJECT;  // infinity: (x, y) = (0, 0) -> false
+    return;
+  }
+  if (inf || oinf) {
+    X = inf ? o.X : acc.X;
+    ZZ = inf ? o.ZZ : acc.ZZ;
+  } else if (!ec_add_chud_x(X, ZZ, acc, o, same_sign)) {
+    verify_exact(A, i);
+    return;
+  }
+  fe zc = ZZ;
+  fe_canon(zc);
+  if (fe_is_zero_canon(zc)) {
+    verify_exact(A, i);
+    return;
+  }
+  verify_finish(A, i, X, ZZ);
 }
 
 // Small batches (verify_device, n <= MBFT_LANE_INV_MAX): one item per LANE
@@ -1709,21 +1611,11 @@ template <bool LANE_INV>
 MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, uint4* buf,
                           const Spill& sp) {
   const long ii = in_batch ? i : 0;
-  uint32_t rw[8], sw[8];
-  load_be256(rw, A.r + 32 * ii);
-  load_be256(sw, A.s + 32 * ii);
-  const uint32_t slot = A.slot[ii];
-  const bool range_ok = !words_is_zero(rw) && words_lt(rw, kNw) &&
-                        !words_is_zero(sw) && words_lt(sw, kNw);
-  KeyDesc kd{A.tabG, (uint32_t)A.wg, 0u};
-  if (slot < A.nslots) kd = A.keys[slot];
-  const bool key_ok = slot < A.nslots && kd.valid;
-  const uint8_t dead_status =
-      key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
-  // a table-free key (window 0) takes no part in the comb: its even lane
-  // runs the ladder at the end
-  const bool tfree = key_ok && key_class_queued(kd.wbits);
-  const bool live = in_batch && key_ok && range_ok && !tfree;
+  Admission ad;
+  admit(ad, A, ii, in_batch);  // (a tfree item: its even lane runs the ladder at the end)
+  const KeyDesc& kd = ad.kd;
+  const uint32_t(&sw)[8] = ad.sw;
+  const bool live = ad.live;
   uint32_t U1[8], U2[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) U1[j] = U2[j] = 0u;
@@ -1768,26 +1660,7 @@ MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, 
   uint32_t carry = 0;
   int step0 = 0;
   if (!qh) {
-    // the first two G windows: affine + affine (zero digits exact, as in
-    // comb_verify_fast)
-    bool neg0, zero0, neg1, zero1;
-    const uint32_t i0 = comb_digit(U[0], carry, W, false, neg0, zero0);
-    shr_words(U, W);
-    const uint32_t i1 = comb_digit(U[0], carry, W, false, neg1, zero1);
-    shr_words(U, W);
-    fe x0, y0, x1, y1;
-    load_point(x0, y0, comb_entry(tab, W, 0, i0));
-    load_point(x1, y1, comb_entry(tab, W, 1, i1));
-    ec_add_affine_chud(acc, x0, y0, x1, y1, neg0 != neg1);
-    yneg = !neg0;
-    inf = zero0 && zero1;
-    if (zero0 != zero1) {
-      acc.X = zero0 ? x1 : x0;
-      acc.Y = zero0 ? y1 : y0;
-      fe_one_mont(acc.ZZ);
-      fe_one_mont(acc.ZZZ);
-      yneg = zero0 ? neg1 : neg0;
-    }
+    comb_start_affine(acc, inf, yneg, U, carry, tab, W);
     step0 = 2;
   }
   StepClock sc;
@@ -1796,42 +1669,15 @@ MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, 
   fe_norm_lazy(acc.ZZZ);
   // the odd lane's half to the even lane
   chud o;
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    o.X.v[k] = __shfl_xor(acc.X.v[k], 1);
-    o.Y.v[k] = __shfl_xor(acc.Y.v[k], 1);
-    o.ZZ.v[k] = __shfl_xor(acc.ZZ.v[k], 1);
-    o.ZZZ.v[k] = __shfl_xor(acc.ZZZ.v[k], 1);
-  }
+  chud_shfl_xor(o, acc, 1);
   const bool oinf = __shfl_xor(inf ? 1 : 0, 1) != 0;
   const bool oyneg = __shfl_xor(yneg ? 1 : 0, 1) != 0;
   if (qh) return;
   if (!live) {
-    if (in_batch && tfree && range_ok)
-      verify_ladder_inline(A, i);
-    else if (in_batch)
-      A.status[i] = dead_status;
+    verify_dead(A, i, in_batch, ad);
     return;
   }
-  fe X, ZZ;
-  if (inf && oinf) {
-    A.status[i] = ST_REJECT;  // infinity: (x, y) = (0, 0) -> false
-    return;
-  }
-  if (inf || oinf) {
-    X = inf ? o.X : acc.X;
-    ZZ = inf ? o.ZZ : acc.ZZ;
-  } else if (!ec_add_chud_x(X, ZZ, acc, o, yneg == oyneg)) {
-    verify_exact(A, i);  // u1 G == +-u2 Q
-    return;
-  }
-  fe zc = ZZ;
-  fe_canon(zc);
-  if (fe_is_zero_canon(zc)) {
-    verify_exact(A, i);
-    return;
-  }
-  verify_finish(A, i, X, ZZ);
+  verify_join(A, i, acc, inf, o, oinf, yneg == oyneg);
 }
 
 // Mid-size batches (k_verify_quads): one item per lane QUAD, s^-1 from the
@@ -1856,21 +1702,11 @@ MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, 
 template <bool INLINE>
 MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uint4* buf, const Spill& sp) {
   const long ii = in_batch ? i : 0;
-  uint32_t rw[8], sw[8];
-  load_be256(rw, A.r + 32 * ii);
-  load_be256(sw, A.s + 32 * ii);
-  const uint32_t slot = A.slot[ii];
-  const bool range_ok = !words_is_zero(rw) && words_lt(rw, kNw) &&
-                        !words_is_zero(sw) && words_lt(sw, kNw);
-  KeyDesc kd{A.tabG, (uint32_t)A.wg, 0u};
-  if (slot < A.nslots) kd = A.keys[slot];
-  const bool key_ok = slot < A.nslots && kd.valid;
-  const uint8_t dead_status =
-      key_ok ? ST_REJECT : ((A.host_status & kArgHostStatus) && slot >= kHostSlot ? (uint8_t)slot : ST_BAD_KEY);
-  // a table-free key (window 0) takes no part in the comb: its even lane
-  // runs the ladder at the end
-  const bool tfree = key_ok && key_class_queued(kd.wbits);
-  const bool live = in_batch && key_ok && range_ok && !tfree;
+  Admission ad;
+  admit(ad, A, ii, in_batch);  // (a tfree item: its first lane runs the ladder at the end)
+  const KeyDesc& kd = ad.kd;
+  const uint32_t(&sw)[8] = ad.sw;
+  const bool live = ad.live;
   uint32_t U1[8], U2[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) U1[j] = U2[j] = 0u;
@@ -1934,25 +1770,7 @@ MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uin
     }
     step0 = mid;
   } else if (!qh) {
-    // G's first two windows: affine + affine (as verify_pair)
-    bool neg0, zero0, neg1, zero1;
-    const uint32_t i0 = comb_digit(U[0], carry, W, false, neg0, zero0);
-    shr_words(U, W);
-    const uint32_t i1 = comb_digit(U[0], carry, W, false, neg1, zero1);
-    shr_words(U, W);
-    fe x0, y0, x1, y1;
-    load_point(x0, y0, comb_entry(tab, W, 0, i0));
-    load_point(x1, y1, comb_entry(tab, W, 1, i1));
-    ec_add_affine_chud(acc, x0, y0, x1, y1, neg0 != neg1);
-    yneg = !neg0;
-    inf = zero0 && zero1;
-    if (zero0 != zero1) {
-      acc.X = zero0 ? x1 : x0;
-      acc.Y = zero0 ? y1 : y0;
-      fe_one_mont(acc.ZZ);
-      fe_one_mont(acc.ZZZ);
-      yneg = zero0 ? neg1 : neg0;
-    }
+    comb_start_affine(acc, inf, yneg, U, carry, tab, W);
     step0 = 2;
   }
   StepClock sc;
@@ -1962,13 +1780,7 @@ MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uin
   if (!inf && yneg) fe_neg(acc.Y, acc.Y);  // the true Y from here on
   // level 1: lanes 0 / 2 take the high half from lanes 1 / 3
   chud o;
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    o.X.v[k] = __shfl_xor(acc.X.v[k], 1);
-    o.Y.v[k] = __shfl_xor(acc.Y.v[k], 1);
-    o.ZZ.v[k] = __shfl_xor(acc.ZZ.v[k], 1);
-    o.ZZZ.v[k] = __shfl_xor(acc.ZZZ.v[k], 1);
-  }
+  chud_shfl_xor(o, acc, 1);
   const bool oinf = __shfl_xor(inf ? 1 : 0, 1) != 0;
   if (high) return;
   bool degen = false;
@@ -1985,46 +1797,19 @@ MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uin
     }
   }
   // level 2: lane 0 takes Q's sum from lane 2
-#pragma unroll
-  for (int k = 0; k < NL; k++) {
-    o.X.v[k] = __shfl_xor(acc.X.v[k], 2);
-    o.Y.v[k] = __shfl_xor(acc.Y.v[k], 2);
-    o.ZZ.v[k] = __shfl_xor(acc.ZZ.v[k], 2);
-    o.ZZZ.v[k] = __shfl_xor(acc.ZZZ.v[k], 2);
-  }
+  chud_shfl_xor(o, acc, 2);
   const bool qinf = __shfl_xor(inf ? 1 : 0, 2) != 0;
   const bool qdegen = __shfl_xor(degen ? 1 : 0, 2) != 0;
   if (qh) return;
   if (!live) {
-    if (in_batch && tfree && range_ok)
-      verify_ladder_inline(A, i);
-    else if (in_batch)
-      A.status[i] = dead_status;
+    verify_dead(A, i, in_batch, ad);
     return;
   }
   if (degen || qdegen) {
     verify_exact(A, i);
     return;
   }
-  fe X, ZZ;
-  if (inf && qinf) {
-    A.status[i] = ST_REJECT;  // infinity: (x, y) = (0, 0) -> false
-    return;
-  }
-  if (inf || qinf) {
-    X = inf ? o.X : acc.X;
-    ZZ = inf ? o.ZZ : acc.ZZ;
-  } else if (!ec_add_chud_x(X, ZZ, acc, o, true)) {
-    verify_exact(A, i);  // u1 G == +-u2 Q
-    return;
-  }
-  fe zc = ZZ;
-  fe_canon(zc);
-  if (fe_is_zero_canon(zc)) {
-    verify_exact(A, i);
-    return;
-  }
-  verify_finish(A, i, X, ZZ);
+  verify_join(A, i, acc, inf, o, qinf, true);  // (both Ys true since level 1)
 }
 
 // The signed-digit comb sum of windows [lo, hi) of one scalar (U: its
@@ -2217,6 +2002,8 @@ MBFT_DEV void split_item(const VerifyArgs& A, long i, uint32_t (&part)[NP][4 * N
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const bool qh = half < 0 ? wave >= 2 : half == 1;  // this wave's scalar: u2 (Q) or u1 (G)
   // every input load issued at once (zero-copy staging: one PCIe round trip)
+  // (admit's rules, open-coded: through the helper the resident kernels'
+  // scratch and this kernel's registers moved)
   uint32_t ew[8], rw[8], sw[8], U[8];
   load_be256(ew, A.e + 32 * i);
   load_be256(rw, A.r + 32 * i);
@@ -2666,9 +2453,6 @@ __global__ void __launch_bounds__(256, 2) k_verify_quads(VerifyArgs A) {
   }
 }
 
-// Grid-stride over items: the default grid has one 256-item block per 256
-// items; a capped grid (MBFT_VERIFY_BPC blocks per CU) leaves wave slots
-// free so the next batch's s^-1 kernels run concurrently.
 // The exact path for the items k_verify queued: both phases recomputed with
 // complete additions (doubling, infinity), one item per thread, grid-stride
 // over the queue (its length is known only on the device).  A final
@@ -2727,6 +2511,9 @@ extern "C" int mbft_debug_verify_clock(double out[3], int reset) {
 }
 #endif
 
+// Grid-stride over items: the default grid has one 256-item block per 256
+// items; a capped grid (MBFT_VERIFY_BPC blocks per CU) leaves wave slots
+// free so the next batch's s^-1 kernels run concurrently.
 template <int MINW>
 __global__ void __launch_bounds__(256, MINW) k_verify(VerifyArgs A) {
 #ifdef MBFT_CLOCK_STAMP
@@ -2737,20 +2524,14 @@ __global__ void __launch_bounds__(256, MINW) k_verify(VerifyArgs A) {
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);
 #endif
-#ifdef MBFT_TWO_DEEP_GATHER
-  __shared__ uint4 coop[2][4][256];  // per wave: two slots of 64 entries x 64 B (gather_issue)
-  uint4* buf2 = coop[1][threadIdx.x >> 6];
-#else
-  __shared__ uint4 coop[1][4][256];  // per wave: one slot of 64 entries x 64 B (gather_issue)
-  uint4* buf2 = nullptr;
-#endif
-  uint4* buf = coop[0][threadIdx.x >> 6];
+  __shared__ uint4 coop[4][256];  // per wave: one slot of 64 entries x 64 B (gather_issue)
+  uint4* buf = coop[threadIdx.x >> 6];
   const long stride = (long)gridDim.x * blockDim.x;
   // block-uniform loop: all lanes of a wave take part in every step
 #pragma unroll 1
   for (long base = (long)blockIdx.x * blockDim.x; base < A.n; base += stride) {
     const long i = base + threadIdx.x;
-    verify_one(A, i, i < A.n, buf, buf2);
+    verify_one(A, i, i < A.n, buf);
   }
 #ifdef MBFT_CLOCK_STAMP
   if (threadIdx.x == 0) {
@@ -3392,19 +3173,6 @@ hipError_t sign(const uint8_t* priv, const uint32_t* key_idx, const uint8_t* e, 
   return hipGetLastError();
 }
 
-// The verifier's queue + scratch buffer: the exact-path queue (n words), its
-// length, the table-free queue's length (the two counters side by side: one
-// memset zeroes both), then (64-word aligned) the table-free queue (n words)
-// and (64-word aligned) 36 planes of one word per grid thread for the rare
-// comb steps' spills (comb_run).  Both queues are there for every path,
-// whatever form the batch takes.
-size_t verify_scratch_offset(long n) { return (ladder_queue_offset(n) + (size_t)n + 63) & ~(size_t)63; }
-size_t verify_words(long n, bool pairs) {
-  // (small batches: room for k_verify_quads' 4 threads an item)
-  const size_t threads = (size_t)(pairs ? 4 * n : n);
-  return verify_scratch_offset(n) + (size_t)4 * NL * ((threads + 255) & ~(size_t)255);
-}
-
 // k_verify_split's additions: lane-group parallel (default) or sequential
 // (env MBFT_SPLIT_WIDE=0)
 static bool split_wide() {
@@ -3430,121 +3198,98 @@ hipError_t verify_server(const ServerArgs& a, int servers, bool two, hipStream_t
   return hipGetLastError();
 }
 
-hipError_t verify(const uint8_t* e, const uint8_t* r, const uint8_t* s, const uint32_t* slot,
-                  const uint32_t* winv, const uint32_t* tabG, int wg, const KeyDesc* keys,
-                  uint32_t nslots, long n, uint8_t* status, uint32_t* slowq, hipStream_t st,
-                  bool host_status, bool queue_zeroed, long split_max, bool split_winv,
-                  const uint32_t* ndev, uint32_t* planes_ws, int small_form, bool table_free) {
-  if (n <= 0) return hipSuccess;
-  // slowq: n + 1 words (the queue, then its length)
-  VerifyArgs A{e, r, s, slot, winv, tabG, keys, nslots, wg, n, status, slowq, slowq + n,
-               host_status ? 1u : 0u, slowq + verify_scratch_offset(n), 0u, ndev};
-  // the smallest batches: one item per 4-wave workgroup (k_verify_split);
-  // split_max < 0: env MBFT_SPLIT_MAX, default 256 (at most one wave per
-  // SIMD); 0 disables (mbft_set_small_batch_form)
-  static const long split_env = env_long("MBFT_SPLIT_MAX", 256L);
-  if (split_max < 0) split_max = split_env;
-  // The small batches' form past the split kernel's: small_form
-  // (mbft_set_small_batch_inverse; -1: the default, 2):
-  // 0 one item per lane pair inverting s per lane (a wave's ~38 us of
-  // divsteps on the critical path); 1 the batched per-wave s^-1 into
-  // planes_ws first, then the lane pairs (same box, one batch at a time,
-  // 300-4,096 items: 87-91 us against 98-101, profiles/round6_planes_ab.json);
-  // 3 the planes, then one item per lane quad (k_verify_quads: 82-84 us at
-  // 768-4,096 items, profiles/round6_quads_ab.json); 2 the lane quads with
-  // the s^-1 by each wave inside the kernel (no separate launch, no planes:
-  // 76-77 us, profiles/round6_quads_inline_ab.json)
-  const int form = small_form < 0 ? 2 : small_form;
-  if (split_winv) {  // host s^-1 R planes (winv): the split kernel's, else unused
-    // (the host stages u1, u2 after the 9 planes: 16 words an item, batch.cpp
-    // host_winv_u)
-    A.uhost = winv + 9 * n;
-    if (n <= split_max) {
-      if (split_wide())
-        hipLaunchKernelGGL(k_verify_split<true>, dim3((unsigned)n), dim3(256), 0, st, A);
-      else
-        hipLaunchKernelGGL(k_verify_split<false>, dim3((unsigned)n), dim3(256), 0, st, A);
-      return hipGetLastError();
-    }
-    if (form >= 2) {  // past it (MBFT_HOST_INV_MAX > split_max): the lane quads on the host's planes
-      A.uhost = nullptr;
-      const long qblocks = (4 * n + 255) / 256;
-      A.sstride = (uint32_t)(qblocks * 256);
-      hipLaunchKernelGGL(k_verify_quads<false>, dim3((unsigned)qblocks), dim3(256), 0, st, A);
-      return hipGetLastError();
-    }
-    winv = nullptr;
-    A.winv = nullptr;
-    A.uhost = nullptr;
-  }
-  // small batches (winv null) run the exact path inline: no queue to reset
-  // table_free (the context holds a table-free key): the second queue's
-  // counter, next to the first, is zeroed here in any case
-  if (winv && (!queue_zeroed || table_free)) {
-    hipError_t me = queue_zeroed ? hipMemsetAsync(slowq + n + 1, 0, 4, st)
-                                 : hipMemsetAsync(slowq + n, 0, table_free ? 8 : 4, st);
-    if (me != hipSuccess) return me;
-  }
-  if (table_free) A.host_status |= kArgTableFree;
-  static const int bpc = (int)env_long("MBFT_VERIFY_BPC", 0);
+long split_max_env() {
+  static const long v = env_long("MBFT_SPLIT_MAX", 256L);
+  return v;
+}
+
+static int device_cus() {
   static const int ncu = [] {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess)
       (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return cus;
   }();
-  if (!winv && n <= split_max) {
-    if (split_wide())
-      hipLaunchKernelGGL(k_verify_split<true>, dim3((unsigned)n), dim3(256), 0, st, A);
-    else
-      hipLaunchKernelGGL(k_verify_split<false>, dim3((unsigned)n), dim3(256), 0, st, A);
-    return hipGetLastError();
+  return ncu;
+}
+
+template <bool WIDE>
+static void launch_split(const VerifyArgs& A, hipStream_t st) {
+  hipLaunchKernelGGL(k_verify_split<WIDE>, dim3((unsigned)A.n), dim3(256), 0, st, A);
+}
+
+// The launches of one batch, as its plan says (verify_plan.h; the measurements
+// behind the small forms: profiles/round6_planes_ab.json, round6_quads_ab.json,
+// round6_quads_inline_ab.json).
+hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const VerifyPlan& plan, hipStream_t st) {
+  const long n = b.n;
+  if (n <= 0) return hipSuccess;
+  VerifyArgs A{b.e, b.r, b.s, b.slot, nullptr, t.tabG, t.keys, t.nslots, t.wg, n, b.status, b.slowq, b.slowq + n,
+               b.host_status ? kArgHostStatus : 0u, b.slowq + verify_scratch_offset(n), 0u, b.ndev};
+  const long blocks = (plan.threads + 255) / 256;
+  if (!verify_form_split(plan.form)) A.sstride = (uint32_t)(blocks * 256);
+  if (plan.ninv_first) {
+    hipError_t e0 = launch_ninv_local<1>(b.s, n, b.planes_ws, nullptr, st, b.ndev);
+    if (e0 != hipSuccess) return e0;
+    A.winv = b.planes_ws;
   }
-  if (!winv || ndev) {  // (a device count: the small-batch kernels only)
-    // small batch, exact path inline (form: above)
-    const long pblocks = (2 * n + 255) / 256;
-    A.sstride = (uint32_t)(pblocks * 256);  // <= verify_words(n, true)'s threads
-    if (!winv && planes_ws && form != 0) {
-      if (form == 2) {
-        const long qblocks = (4 * n + 255) / 256;
-        A.sstride = (uint32_t)(qblocks * 256);
-        A.winv = nullptr;
-        hipLaunchKernelGGL(k_verify_quads<true>, dim3((unsigned)qblocks), dim3(256), 0, st, A);
-        return hipGetLastError();
-      }
-      hipError_t e0 = launch_ninv_local<1>(s, n, planes_ws, nullptr, st, ndev);
-      if (e0 != hipSuccess) return e0;
-      A.winv = planes_ws;
-      if (form == 3) {
-        const long qblocks = (4 * n + 255) / 256;
-        A.sstride = (uint32_t)(qblocks * 256);
-        hipLaunchKernelGGL(k_verify_quads<false>, dim3((unsigned)qblocks), dim3(256), 0, st, A);
-        return hipGetLastError();
-      }
-      hipLaunchKernelGGL(k_verify_pairs<false>, dim3((unsigned)pblocks), dim3(256), 0, st, A);
-      return hipGetLastError();
-    }
-    A.winv = nullptr;
-    hipLaunchKernelGGL(k_verify_pairs<true>, dim3((unsigned)pblocks), dim3(256), 0, st, A);
-    return hipGetLastError();
-  }
-  long blocks = (n + 255) / 256;
-  if (bpc > 0 && blocks > (long)bpc * ncu) blocks = (long)bpc * ncu;
   const dim3 grid((unsigned)blocks), block(256);
-  A.sstride = (uint32_t)(blocks * 256);  // <= verify_words' 256-rounded n
-  // MINW = 3 waves/SIMD (the trace summaries under profiles/ name k_verify<3>)
-  hipLaunchKernelGGL((k_verify<3>), grid, block, 0, st, A);
-  // the queued items: a grid of up to kSlowBpc blocks per CU (one wave per
-  // SIMD) that exits at once when the queue is empty
-  constexpr int kSlowBpc = 4;
-  long sblocks = (n + 255) / 256 < (long)ncu * kSlowBpc ? (n + 255) / 256 : (long)ncu * kSlowBpc;
-  if (sblocks > blocks) sblocks = blocks;  // its threads index the same spill planes (A.sstride)
-  if (winv) hipLaunchKernelGGL(k_verify_slow, dim3((unsigned)sblocks), dim3(256), 0, st, A);
-  // the table-free items: two blocks per CU at the most (the kernel's
-  // occupancy), grid-stride over the queue
-  if (winv && table_free) {
-    const long lblocks = (n + 255) / 256 < (long)ncu * 2 ? (n + 255) / 256 : (long)ncu * 2;
-    hipLaunchKernelGGL(k_verify_ladder, dim3((unsigned)lblocks), dim3(256), 0, st, A);
+  switch (plan.form) {
+    case VerifyForm::kSplitHost:
+      A.winv = b.winv;
+      A.uhost = b.winv + 9 * n;
+      [[fallthrough]];
+    case VerifyForm::kSplitWave:
+      if (split_wide())
+        launch_split<true>(A, st);
+      else
+        launch_split<false>(A, st);
+      break;
+    case VerifyForm::kQuadsInline:
+      hipLaunchKernelGGL(k_verify_quads<true>, grid, block, 0, st, A);
+      break;
+    case VerifyForm::kQuadsHost:
+      A.winv = b.winv;
+      [[fallthrough]];
+    case VerifyForm::kQuadsPlanes:
+      hipLaunchKernelGGL(k_verify_quads<false>, grid, block, 0, st, A);
+      break;
+    case VerifyForm::kPairsPlanes:
+      hipLaunchKernelGGL(k_verify_pairs<false>, grid, block, 0, st, A);
+      break;
+    case VerifyForm::kPairsLane:
+      hipLaunchKernelGGL(k_verify_pairs<true>, grid, block, 0, st, A);
+      break;
+    case VerifyForm::kLarge: {
+      A.winv = b.winv;
+      if (t.table_free) {
+        if (plan.queue_reset) {
+          hipError_t me = hipMemsetAsync(b.slowq + n + 1, 0, 4, st);
+          if (me != hipSuccess) return me;
+        }
+        A.host_status |= kArgTableFree;
+      }
+      static const int bpc = (int)env_long("MBFT_VERIFY_BPC", 0);
+      const long ncu = device_cus();
+      const long vblocks = bpc > 0 && blocks > bpc * ncu ? bpc * ncu : blocks;
+      A.sstride = (uint32_t)(vblocks * 256);
+      // MINW = 3 waves/SIMD (the trace summaries under profiles/ name k_verify<3>)
+      hipLaunchKernelGGL((k_verify<3>), dim3((unsigned)vblocks), block, 0, st, A);
+      // the queued items: a grid of up to kSlowBpc blocks per CU (one wave per
+      // SIMD) that exits at once when the queue is empty; its threads index
+      // the same spill planes (A.sstride)
+      constexpr int kSlowBpc = 4;
+      long sblocks = blocks < ncu * kSlowBpc ? blocks : ncu * kSlowBpc;
+      if (sblocks > vblocks) sblocks = vblocks;
+      hipLaunchKernelGGL(k_verify_slow, dim3((unsigned)sblocks), block, 0, st, A);
+      // the table-free items: two blocks per CU at the most (the kernel's
+      // occupancy), grid-stride over the queue
+      if (t.table_free) {
+        const long lblocks = blocks < ncu * 2 ? blocks : ncu * 2;
+        hipLaunchKernelGGL(k_verify_ladder, dim3((unsigned)lblocks), block, 0, st, A);
+      }
+      break;
+    }
   }
   return hipGetLastError();
 }

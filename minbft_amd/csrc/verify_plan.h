@@ -1,0 +1,81 @@
+// The verifier's launch plan: the kernel form a batch takes, its grid and what
+// runs before it, decided ONCE -- verify_device sizes the batch's `slowq`
+// buffer from it and mbft_launch::verify launches it.  Plain C++, no HIP.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace mbft {
+
+// The small-batch forms (all but kLarge) run the exact path and the table-free
+// keys inline; kLarge queues both (k_verify_slow, k_verify_ladder).
+enum class VerifyForm : int {
+  kSplitHost,    // k_verify_split, one item per workgroup; s^-1 R and u1, u2 staged by the host
+  kSplitWave,    // k_verify_split, every wave inverts s itself
+  kQuadsInline,  // k_verify_quads<true>: one item per lane quad, s^-1 by each wave in the kernel
+  kQuadsPlanes,  // k_ninv_local<1> into the planes workspace, then k_verify_quads<false>
+  kQuadsHost,    // k_verify_quads<false> on the host's planes
+  kPairsPlanes,  // k_ninv_local<1>, then k_verify_pairs<false>: one item per lane pair
+  kPairsLane,    // k_verify_pairs<true>: s^-1 by each lane
+  kLarge         // k_verify<3>, one item per lane, on the batch's planes
+};
+constexpr bool verify_form_split(VerifyForm f) { return f == VerifyForm::kSplitHost || f == VerifyForm::kSplitWave; }
+
+// Where s^-1 comes from: the form itself, the batch's own s^-1 kernels
+// (verify_device runs them first), the host's planes.
+enum class InvSource : int { kNone, kBatch, kHost };
+
+// has_count: n is an upper bound, the count is on the device -- the small-batch
+// kernels only, which read it (a batched chain is sized by n on the host).
+constexpr InvSource verify_inv_source(long n, size_t lane_inv_max, bool host_planes, bool has_count) {
+  return host_planes ? InvSource::kHost
+                     : ((size_t)n <= lane_inv_max || has_count) ? InvSource::kNone : InvSource::kBatch;
+}
+
+struct VerifyPlan {
+  VerifyForm form;
+  long threads;      // the grid's threads (256 a block); kLarge: before the MBFT_VERIFY_BPC cap
+  bool ninv_first;   // k_ninv_local<1> into the planes workspace runs first
+  bool queue_reset;  // a memset resets the table-free queue's counter in front of the kernel (where
+                     // a key of that class exists; the exact-path queue's: the s^-1 kernels)
+};
+
+// split_max: 0 disables the split form.  small_form (0 .. 3,
+// mbft_set_small_batch_inverse) is the form past it: 0 lane pairs inverting
+// per lane, 1 lane pairs on planes, 2 lane quads inverting in the kernel, 3
+// lane quads on planes; without a planes workspace only 0 is left.  Host
+// planes past split_max (MBFT_HOST_INV_MAX above it) serve the lane quads;
+// under small_form < 2 they are dropped.
+constexpr VerifyPlan verify_plan(long n, InvSource src, bool has_count, bool has_planes_ws, long split_max,
+                                 int small_form) {
+  if (src == InvSource::kHost) {
+    if (n <= split_max) return {VerifyForm::kSplitHost, 256 * n, false, false};
+    if (small_form >= 2) return {VerifyForm::kQuadsHost, 4 * n, false, false};
+    src = InvSource::kNone;
+  }
+  if (src == InvSource::kBatch && !has_count) return {VerifyForm::kLarge, n, false, true};
+  if (src == InvSource::kNone) {
+    if (n <= split_max) return {VerifyForm::kSplitWave, 256 * n, false, false};
+    if (has_planes_ws && small_form == 2) return {VerifyForm::kQuadsInline, 4 * n, false, false};
+    if (has_planes_ws && small_form == 3) return {VerifyForm::kQuadsPlanes, 4 * n, true, false};
+    if (has_planes_ws && small_form != 0) return {VerifyForm::kPairsPlanes, 2 * n, true, false};
+  }
+  return {VerifyForm::kPairsLane, 2 * n, false, false};
+}
+
+// `slowq`: the exact-path queue (n words), its length, the table-free queue's
+// length (side by side), then (64-word aligned) the table-free queue (n
+// words) and (64-word aligned) kSpillPlanes planes of one word per grid
+// thread for the rare comb steps' spills.  Both queues are there for every
+// form; the split forms spill nothing.
+constexpr int kSpillPlanes = 36;
+constexpr size_t ladder_queue_offset(long n) { return ((size_t)n + 2 + 63) & ~(size_t)63; }
+constexpr size_t verify_scratch_offset(long n) { return (ladder_queue_offset(n) + (size_t)n + 63) & ~(size_t)63; }
+constexpr size_t verify_spill_threads(const VerifyPlan& p) {
+  return verify_form_split(p.form) ? 0 : ((size_t)p.threads + 255) & ~(size_t)255;
+}
+constexpr size_t verify_slowq_words(long n, const VerifyPlan& p) {
+  return verify_scratch_offset(n) + (size_t)kSpillPlanes * verify_spill_threads(p);
+}
+
+}  // namespace mbft

@@ -1,8 +1,9 @@
 // Does s_waitcnt vmcnt(N > 0) order a ds_read behind an older
 // global_load_lds_dwordx4 when a younger one is still in flight?  Each wave
 // keeps two LDS slots and two cooperative-style gathers of random 64-B table
-// entries in flight (the k_verify two-deep pipeline, kernels.hip
-// comb_verify_fast2), reads the older slot after vmcnt(4) (or vmcnt(0)), and
+// entries in flight (the two-deep gather pipeline k_verify once had; measured
+// no faster and removed), reads the older slot after vmcnt(4)
+// (or vmcnt(0)), and
 // counts 16-B chunks whose content is not the expected function of the entry
 // index.  Diagnostic only (round 5).
 //   hipcc --offload-arch=gfx950 -O3 -o tools/ubench_lds_dma_order tools/ubench_lds_dma_order.hip
