@@ -68,6 +68,7 @@ import (
 	"crypto/elliptic"
 	"fmt"
 	"math/big"
+	"sync/atomic"
 	"unsafe"
 
 	"github.com/hyperledger-labs/minbft/api"
@@ -150,6 +151,24 @@ type Config struct {
 	// its key store has (keymanager.go:96-101), so that key is registered
 	// (at its role's window) before the call's batch runs (keys.go).
 	KeyStore PublicKeyStore
+	// HotKeys, if PromoteEvery > 0, turns the per-key use counts on
+	// (mbft_set_key_accounting) and, every PromoteEvery batches -- each
+	// VerifyBatch and each CheckMessages that reached the GPU counts as one;
+	// lone VerifyMessageAuthenTag calls are counted by the library but do not
+	// advance the clock -- re-classes the most used keys of a cheaper class into PromoteClass
+	// (mbft_promote_hot_keys; keys.go).  Off by default: nothing is counted
+	// and no key changes class on its own.
+	HotKeys HotKeys
+}
+
+// HotKeys is the promotion policy of Config.HotKeys.  Class is a key class
+// code: a comb window 4..29, or KeyClassTeeth(t).  A promotion costs one
+// device synchronize, so PromoteEvery should be hundreds of batches.
+type HotKeys struct {
+	PromoteEvery int
+	Class        uint32
+	MaxKeys      int
+	MinUses      uint64
 }
 
 // Authenticator implements api.Authenticator and api.MessageBatchChecker on
@@ -164,6 +183,10 @@ type Authenticator struct {
 
 	// the USIGAuthen public keys New was given (USIG.VerifyUI finds a USIG ID's replica here)
 	usigKeys map[uint32]*ecdsa.PublicKey
+
+	hot        HotKeys      // Config.HotKeys
+	batches    uint64       // VerifyBatch and CheckMessages batches so far (atomic; the promotion's clock)
+	promoteErr atomic.Value // string: the last promotion's failure, "" after one that worked
 
 	arenas arenaPool   // batches are marshalled here (library page-locked memory)
 	keys   keyRegistry // the (role, id) pairs the context holds (keys.go)
@@ -273,6 +296,12 @@ func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnable
 		if rc := C.mbft_set_resident(ctx, C.int(slots)); rc != C.MBFT_OK {
 			return fail("mbft_set_resident", rc)
 		}
+	}
+	if cfg.HotKeys.PromoteEvery > 0 {
+		if rc := C.mbft_set_key_accounting(ctx, 1); rc != C.MBFT_OK {
+			return fail("mbft_set_key_accounting", rc)
+		}
+		a.hot = cfg.HotKeys
 	}
 	return a, nil
 }
@@ -433,6 +462,7 @@ func (a *Authenticator) VerifyBatch(calls []Call) []error {
 		a.arenas.put(ar)
 		if n == 1 {
 			out[0] = a.VerifyMessageAuthenTag(calls[0].Role, calls[0].ID, calls[0].Msg, calls[0].Tag)
+			a.promoteTick()
 			return out
 		}
 		copy(out, a.VerifyBatch(calls[:n/2]))
@@ -458,6 +488,7 @@ func (a *Authenticator) VerifyBatch(calls []Call) []error {
 	for i := range calls {
 		out[i] = a.statusToErr(calls[i].Role, calls[i].ID, int(st[i]))
 	}
+	a.promoteTick()
 	return out
 }
 

@@ -16,7 +16,11 @@ package gpuauth
 //     state, exactly what the reference gives: the batch runs as if the key
 //     had been there from the start.  An id the store does not have is
 //     remembered as absent (the store is static) and rejected as the
-//     reference rejects it (a nil key, crypto.go:85-88 / :192-195).
+//     reference rejects it (a nil key, crypto.go:85-88 / :192-195);
+//   - RemoveKey, SetKeyClass, KeyUsage and PromoteHotKeys are the life of a
+//     key after that (include/minbft_gpu.h): a client that left gives its
+//     slot and table back, a hot key gets a table.  A removed key that the
+//     store still has comes back through ensureKey on its next call.
 
 /*
 #include "minbft_gpu.h"
@@ -30,6 +34,7 @@ import (
 	"io/ioutil"
 	"sort"
 	"sync"
+	"sync/atomic"
 	"unsafe"
 
 	yaml "gopkg.in/yaml.v2"
@@ -185,4 +190,89 @@ func (a *Authenticator) ensureKeys(calls []Call) {
 		last = k
 		a.ensureKey(c.Role, c.ID)
 	}
+}
+
+// KeyClassTeeth is the class code of a compact key of t teeth
+// (MBFT_KEY_CLASS_TEETH, a function-like macro cgo cannot call).
+func KeyClassTeeth(t int) uint32 { return 0x100 | uint32(t) }
+
+// RemoveKey unmaps (role, id) (mbft_remove_public_key): its calls are then
+// rejected like those of an id never registered, and its slot and storage are
+// reused once nothing else maps to them.  With Config.KeyStore set the key is
+// registered again when a call by it arrives and the store still has it.
+func (a *Authenticator) RemoveKey(role api.AuthenticationRole, id uint32) error {
+	a.keys.mu.Lock()
+	defer a.keys.mu.Unlock()
+	rc := C.mbft_remove_public_key(a.ctx, C.uint32_t(roleByte(role)), C.uint32_t(id))
+	if rc != C.MBFT_OK {
+		return a.failure("mbft_remove_public_key", int(rc))
+	}
+	delete(a.keys.known, roleID{role, id})
+	return nil
+}
+
+// SetKeyClass rebuilds the verification data of the registered key
+// (role, id) in class cls: a comb window 4..29, MBFT_WINDOW_NONE or
+// KeyClassTeeth(t).  On failure the key keeps its class.  One device
+// synchronize a call.
+func (a *Authenticator) SetKeyClass(role api.AuthenticationRole, id uint32, cls uint32) error {
+	rc := C.mbft_set_key_class(a.ctx, C.uint32_t(roleByte(role)), C.uint32_t(id), C.uint32_t(cls))
+	if rc != C.MBFT_OK {
+		return a.failure("mbft_set_key_class", int(rc))
+	}
+	return nil
+}
+
+// KeyUsage returns the verifies performed under (role, id) and how many of
+// them were rejected, while Config.HotKeys (or mbft_set_key_accounting) has
+// the counts on; what is not counted: include/minbft_gpu.h.
+func (a *Authenticator) KeyUsage(role api.AuthenticationRole, id uint32) (uses, rejects uint64, err error) {
+	slot := C.mbft_key_slot(a.ctx, C.uint32_t(roleByte(role)), C.uint32_t(id))
+	if slot < 0 {
+		return 0, 0, a.failure("mbft_key_slot", int(slot))
+	}
+	s := C.uint32_t(slot)
+	var u, r C.uint64_t
+	if rc := C.mbft_key_usage(a.ctx, &s, 1, &u, &r); rc != C.MBFT_OK {
+		return 0, 0, a.failure("mbft_key_usage", int(rc))
+	}
+	return uint64(u), uint64(r), nil
+}
+
+// PromoteHotKeys re-classes the maxKeys most used keys of a class cheaper
+// than cls with at least minUses uses into cls (mbft_promote_hot_keys) and
+// returns how many.
+func (a *Authenticator) PromoteHotKeys(cls uint32, maxKeys int, minUses uint64) (int, error) {
+	var n C.size_t
+	rc := C.mbft_promote_hot_keys(a.ctx, C.uint32_t(cls), C.size_t(maxKeys), C.uint64_t(minUses), &n)
+	if rc != C.MBFT_OK {
+		return 0, a.failure("mbft_promote_hot_keys", int(rc))
+	}
+	return int(n), nil
+}
+
+// promoteTick counts a batch (VerifyBatch, CheckMessages) and runs the
+// Config.HotKeys promotion every PromoteEvery of them.  A failed promotion
+// leaves every key as it was; its error is kept for LastPromoteError.
+func (a *Authenticator) promoteTick() {
+	if a.hot.PromoteEvery <= 0 {
+		return
+	}
+	if atomic.AddUint64(&a.batches, 1)%uint64(a.hot.PromoteEvery) != 0 {
+		return
+	}
+	if _, err := a.PromoteHotKeys(a.hot.Class, a.hot.MaxKeys, a.hot.MinUses); err != nil {
+		a.promoteErr.Store(err.Error())
+	} else {
+		a.promoteErr.Store("")
+	}
+}
+
+// LastPromoteError reports the failure of the most recent Config.HotKeys
+// promotion, nil if it worked or none has run yet.
+func (a *Authenticator) LastPromoteError() error {
+	if s, ok := a.promoteErr.Load().(string); ok && s != "" {
+		return fmt.Errorf("%s", s)
+	}
+	return nil
 }

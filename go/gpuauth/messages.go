@@ -67,6 +67,7 @@ func (a *Authenticator) CheckMessages(msgs []api.AuthenMessage, n uint32) (api.C
 		mb.info[i] = msgInfo{typ: m.Type, replica: m.ReplicaID, primary: m.PrepReplicaID,
 			client: m.ClientID, view: m.View}
 	}
+	a.promoteTick() // (a re-class keeps slots and statuses: the unresolved batch is unaffected)
 	return mb, nil
 }
 

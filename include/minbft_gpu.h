@@ -221,6 +221,85 @@ int mbft_get_windows(const mbft_ctx* ctx, int* g_wbits, int* q_wbits);
 #define MBFT_TEETH_MAX 8
 int mbft_set_key_teeth(mbft_ctx* ctx, int teeth);        /* keys registered AFTER the call */
 int mbft_get_key_teeth(const mbft_ctx* ctx, int* teeth); /* 0 while the current class is a window */
+/* THE LIFE OF A KEY AFTER REGISTRATION.  Every call below
+ * that changes the key store waits for the library's batches in flight, like
+ * registration, and is replayed on the peer engines (mbft_ctx_add_device).
+ *
+ * A key's CLASS has one code, the one its descriptor carries: a comb window
+ * 4..29, MBFT_WINDOW_NONE (table-free), or MBFT_KEY_CLASS_TEETH(t) for a
+ * compact key of t = MBFT_TEETH_MIN..MBFT_TEETH_MAX teeth.  Classes are ordered
+ * by the bytes of one key's data (64 B, 64 B x 2^t, the comb table).
+ *
+ * Use counts.  mbft_set_key_accounting(ctx, 1) (default off: nothing is
+ * allocated, no batch launches anything more) makes every batch end with one
+ * more kernel on its stream that adds, per key slot, `uses` -- the batch's
+ * items whose slot is registered and valid -- and `rejects` -- those of them
+ * whose status is not MBFT_ACCEPT -- into 64-bit counters on the GPU, one pair
+ * per slot and engine.  NOT counted, because no slot can be charged: items the
+ * host decided before the signature check (unknown role or id, malformed tag,
+ * ...), items whose slot number is not registered, and items under an invalid
+ * or released slot.  The counts are VERIFIES PERFORMED, not calls received: the
+ * message layer verifies identical calls once and counts them once.  Single
+ * calls served by the resident verifier are counted on the host and merged
+ * when the counts are read.  Sharded batches are counted shard by shard.
+ *   mbft_key_usage: uses_out[i] / rejects_out[i] (either may be NULL) of
+ *     slots[i], or of slot i when slots is NULL, summed over the engines and
+ *     the resident counter; 0 for a slot that does not exist.  It waits for the
+ *     library's batches and synchronizes the library's own streams; work a
+ *     caller queued on a stream of its own (mbft_verify_prehashed_device) is
+ *     counted once that stream has finished -- synchronize it first.
+ *   mbft_reset_key_usage: every counter back to zero (synchronizes the
+ *     device).  A released slot's counters are zeroed; mbft_clear_keys zeroes
+ *     all.  Counters live for the context, not across processes.
+ *
+ * Re-classing.  mbft_set_key_class rebuilds the verification data of the
+ * registered key (role, id) in class cls; mbft_set_slot_classes does it for n
+ * slots at once.  The new data is built first, then the descriptors are
+ * swapped, then the old storage is released: on MBFT_ERR_NOMEM or any other
+ * failure the keys keep their class and go on verifying.  Slots already in cls
+ * are skipped; an unknown class code is MBFT_ERR_ARG; an invalid slot is
+ * MBFT_ERR_ARG in the single form and skipped in the bulk form (a slot number
+ * that does not exist is MBFT_ERR_ARG in both).  Each call that changes
+ * anything costs ONE device synchronize per engine (the resident verifier is
+ * parked first), whatever n is: the bulk form exists to share it.  Use counts
+ * are kept.
+ *   mbft_get_key_class: the class of (role, id) and the bytes of its data.
+ *   mbft_promote_hot_keys: of the valid keys whose class is cheaper in memory
+ *     than cls and whose uses are >= min_uses, the max_keys with the most uses
+ *     (ties: the lower slot) are re-classed into cls in one bulk call;
+ *     *promoted receives how many were chosen.
+ *
+ * Removal.  mbft_remove_public_key unmaps (role, id) (MBFT_ERR_KEY when it is
+ * not mapped): the pair then reads MBFT_UNKNOWN_KEY through every entry point,
+ * like an id never registered, and may be registered again, with the same or
+ * another key.  A slot is RELEASED when no (role, id) maps to it any more and
+ * its number was not handed out by mbft_register_points; mbft_release_slots
+ * gives that claim up (and releases the slots nothing maps to).  A released
+ * slot is invalid -- device entry points that still name it read MBFT_BAD_KEY
+ * -- its number is taken first, lowest first, by the next registration, and
+ * its storage by the next single-key registration or re-class of its class,
+ * so neither the descriptor array nor the key blocks grow under churn.  A call
+ * that releases slots costs one device synchronize per engine.  Mapping a
+ * registered pair to ANOTHER key with mbft_set_public_key_* (rotation by
+ * overwriting) releases the pair's earlier slot under the same rule, at the
+ * same cost.
+ *   mbft_key_memory: out[0] bytes of live key data, out[1] bytes of released
+ *     pieces awaiting reuse, out[2] bytes of key blocks held, on the
+ *     context's own engine. */
+#define MBFT_KEY_CLASS_TEETH(t) (0x100 | (t))
+int mbft_set_key_accounting(mbft_ctx* ctx, int enabled);
+int mbft_key_usage(mbft_ctx* ctx, const uint32_t* slots, size_t n, uint64_t* uses_out,
+                   uint64_t* rejects_out);
+int mbft_reset_key_usage(mbft_ctx* ctx);
+int mbft_get_key_class(const mbft_ctx* ctx, uint32_t role, uint32_t id, uint32_t* cls,
+                       uint64_t* table_bytes);
+int mbft_set_key_class(mbft_ctx* ctx, uint32_t role, uint32_t id, uint32_t cls);
+int mbft_set_slot_classes(mbft_ctx* ctx, const uint32_t* slots, size_t n, uint32_t cls);
+int mbft_promote_hot_keys(mbft_ctx* ctx, uint32_t cls, size_t max_keys, uint64_t min_uses,
+                          size_t* promoted);
+int mbft_remove_public_key(mbft_ctx* ctx, uint32_t role, uint32_t id);
+int mbft_release_slots(mbft_ctx* ctx, const uint32_t* slots, size_t n);
+int mbft_key_memory(const mbft_ctx* ctx, uint64_t out[3]);
 /* USIG scheme present (authenticator.go:102-110: absent without a USIG). */
 int mbft_enable_usig(mbft_ctx* ctx, int enabled);
 /* Private key for GenerateMessageAuthenTag in an ECDSA role. */

@@ -47,6 +47,12 @@ WINDOW_NONE = 0
 #: teeth of compact keys (MBFT_TEETH_MIN, MBFT_TEETH_MAX)
 TEETH_MIN, TEETH_MAX = 2, 8
 
+
+def key_class_teeth(t: int) -> int:
+    """The class code of a compact key of t teeth (MBFT_KEY_CLASS_TEETH)."""
+    return 0x100 | t
+
+
 #: bytes per tag slot of the batch signer (MBFT_TAG_SLOT)
 TAG_SLOT = 72
 #: bytes per UI slot of the software USIG (MBFT_UI_SLOT) and of its identity
@@ -82,6 +88,9 @@ EXPORTED = [
     "mbft_usig_init", "mbft_usig_id", "mbft_usig_next_counter", "mbft_usig_create_uis_digests",
     "mbft_usig_create_uis_flat", "mbft_usig_sign_messages_flat",
     "mbft_set_key_teeth", "mbft_get_key_teeth",
+    "mbft_set_key_accounting", "mbft_key_usage", "mbft_reset_key_usage",
+    "mbft_get_key_class", "mbft_set_key_class", "mbft_set_slot_classes", "mbft_promote_hot_keys",
+    "mbft_remove_public_key", "mbft_release_slots", "mbft_key_memory",
 ]
 
 # enum mbft_msg_type / mbft_stage / mbft_validate_flags
@@ -232,6 +241,16 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_set_generator_window": (i, [vp, i]),
         "mbft_set_key_teeth": (i, [vp, i]),
         "mbft_get_key_teeth": (i, [vp, ctypes.POINTER(i)]),
+        "mbft_set_key_accounting": (i, [vp, i]),
+        "mbft_key_usage": (i, [vp, vp, sz, vp, vp]),
+        "mbft_reset_key_usage": (i, [vp]),
+        "mbft_get_key_class": (i, [vp, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint64)]),
+        "mbft_set_key_class": (i, [vp, u32, u32, u32]),
+        "mbft_set_slot_classes": (i, [vp, vp, sz, u32]),
+        "mbft_promote_hot_keys": (i, [vp, u32, sz, ctypes.c_uint64, ctypes.POINTER(sz)]),
+        "mbft_remove_public_key": (i, [vp, u32, u32]),
+        "mbft_release_slots": (i, [vp, vp, sz]),
+        "mbft_key_memory": (i, [vp, vp]),
         "mbft_get_windows": (i, [vp, ctypes.POINTER(i), ctypes.POINTER(i)]),
         "mbft_request_digests_device": (i, [vp, vp, vp, u32, sz, vp, vp]),
         "mbft_sha256_device": (i, [vp, vp, vp, sz, vp, vp]),

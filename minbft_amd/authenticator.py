@@ -191,6 +191,73 @@ class Authenticator:
         self._check(self.lib.mbft_get_key_teeth(self.ctx, ctypes.byref(t)), "get_key_teeth")
         return t.value
 
+    # -------------------------------------------- a key's life after registration
+    def set_key_accounting(self, enabled: bool):
+        """Per-key use counts on the GPU (off by default): while on, every
+        batch ends with one more kernel that adds each slot's uses and rejects
+        (include/minbft_gpu.h says what is not counted)."""
+        self._check(self.lib.mbft_set_key_accounting(self.ctx, 1 if enabled else 0), "set_key_accounting")
+
+    def key_usage(self, slots=None, n: int = 0):
+        """(uses, rejects) as uint64 arrays: of ``slots``, or of slots
+        0..n-1 when ``slots`` is None; summed over engines and the resident
+        verifier's counter."""
+        if slots is not None:
+            slots = np.ascontiguousarray(slots, dtype=np.uint32)
+            n = len(slots)
+        uses = np.zeros(n, dtype=np.uint64)
+        rej = np.zeros(n, dtype=np.uint64)
+        self._check(self.lib.mbft_key_usage(self.ctx, slots.ctypes.data if slots is not None else None, n,
+                                            uses.ctypes.data, rej.ctypes.data), "key_usage")
+        return uses, rej
+
+    def reset_key_usage(self):
+        self._check(self.lib.mbft_reset_key_usage(self.ctx), "reset_key_usage")
+
+    def key_class(self, role: int, key_id: int) -> Tuple[int, int]:
+        """(class code, bytes of key data) of a registered (role, id): a comb
+        window 4..29, 0 (table-free) or ``_lib.key_class_teeth(t)``."""
+        cls, nb = ctypes.c_uint32(), ctypes.c_uint64()
+        self._check(self.lib.mbft_get_key_class(self.ctx, role, key_id, ctypes.byref(cls), ctypes.byref(nb)),
+                    "get_key_class")
+        return cls.value, nb.value
+
+    def set_key_class(self, role: int, key_id: int, cls: int):
+        """Rebuild a registered key's verification data in class ``cls``; on
+        failure it keeps its class.  Costs one device synchronize."""
+        self._check(self.lib.mbft_set_key_class(self.ctx, role, key_id, cls), "set_key_class")
+
+    def set_slot_classes(self, slots, cls: int):
+        """The bulk form: every valid slot of ``slots`` into ``cls``, one
+        device synchronize in all."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        self._check(self.lib.mbft_set_slot_classes(self.ctx, slots.ctypes.data, len(slots), cls),
+                    "set_slot_classes")
+
+    def promote_hot_keys(self, cls: int, max_keys: int, min_uses: int) -> int:
+        """Re-class the ``max_keys`` most used keys of a cheaper class with at
+        least ``min_uses`` uses into ``cls``; returns how many."""
+        k = ctypes.c_size_t()
+        self._check(self.lib.mbft_promote_hot_keys(self.ctx, cls, max_keys, min_uses, ctypes.byref(k)),
+                    "promote_hot_keys")
+        return k.value
+
+    def remove_public_key(self, role: int, key_id: int):
+        """Unmap (role, id); its slot is released when nothing else uses it."""
+        self._check(self.lib.mbft_remove_public_key(self.ctx, role, key_id), "remove_public_key")
+
+    def release_slots(self, slots):
+        """Give up slot numbers ``register_points`` handed out."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        self._check(self.lib.mbft_release_slots(self.ctx, slots.ctypes.data, len(slots)), "release_slots")
+
+    def key_memory(self) -> Tuple[int, int, int]:
+        """(bytes of live key data, bytes of released pieces, bytes of key
+        blocks held) on the context's own engine."""
+        out = (ctypes.c_uint64 * 3)()
+        self._check(self.lib.mbft_key_memory(self.ctx, out), "key_memory")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def set_generator_window(self, wbits: int):
         """Rebuild the generator comb table with a window of 4..29 bits."""
         self._check(self.lib.mbft_set_generator_window(self.ctx, wbits), "set_generator_window")

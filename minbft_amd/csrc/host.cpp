@@ -144,15 +144,30 @@ int hip_fail(mbft_ctx* c, hipError_t e, const char* what) {
   return fail(c, MBFT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-// Upload the slot descriptors (small: 16 B per slot).
+// Upload the slot descriptors (16 B per slot): the entries marked dirty since
+// the last upload, a run of neighbours as one copy; all of them when d_keys
+// has just grown (its new block holds nothing yet).
 int upload_keydesc(mbft_ctx* c) {
-  if (c->keydesc.empty()) return MBFT_OK;
-  HIPCHK(c, c->d_keys.ensure(c->keydesc.size() * sizeof(mbft::KeyDesc)));
-  HIPCHK(c, hipMemcpyAsync(c->d_keys.p, c->keydesc.data(),
-                           c->keydesc.size() * sizeof(mbft::KeyDesc), hipMemcpyHostToDevice,
-                           c->stream));
+  const size_t ns = c->keydesc.size();
+  if (ns == 0) {
+    c->kd_dirty.clear();
+    return MBFT_OK;
+  }
+  const void* before = c->d_keys.p;
+  HIPCHK(c, c->d_keys.ensure(ns * sizeof(mbft::KeyDesc)));
+  if (c->d_keys.p != before) {
+    c->kd_dirty.clear();
+    c->kd_dirty.mark(0, ns);
+  }
+  for (const auto& r : c->kd_dirty.ranges()) {
+    const size_t lo = r.first, hi = r.second < ns ? r.second : ns;
+    if (lo >= hi) continue;
+    HIPCHK(c, hipMemcpyAsync(c->d_keys.as<mbft::KeyDesc>() + lo, c->keydesc.data() + lo,
+                             (hi - lo) * sizeof(mbft::KeyDesc), hipMemcpyHostToDevice, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  return MBFT_OK;
+  c->kd_dirty.clear();
+  return c->accounting.load() ? grow_key_counters(c) : MBFT_OK;
 }
 
 // (Re)build the generator comb table with window w.  The old table is freed
@@ -234,13 +249,146 @@ void set_key_class(mbft_ctx* c, uint32_t cls) {
   c->q_wbits = cls >= mbft::kTeethFlag ? mbft_launch::kWindowNone : (int)cls;
 }
 
+namespace {
+
+// One fresh run of storage for cnt keys of class cls, as registration always
+// took it: table-free entries and compact tables from pooled chunks (a call
+// with many keys takes a block of its own), comb tables in one block a call.
+int fresh_run(mbft_ctx* c, uint32_t cls, size_t cnt, uint32_t** out) {
+  uint32_t* dst = nullptr;
+  if (cls >= mbft::kTeethFlag) {
+    const int t = (int)(cls & 0xFFu);
+    const size_t tw = mbft_launch::teeth_table_words(t);
+    const size_t per_chunk = mbft_ctx::kTeethChunk / (tw * 4);
+    if (cnt <= c->teeth_left[t]) {
+      dst = c->teeth_chunk[t];
+    } else {
+      const size_t tabs = cnt >= per_chunk / 4 ? cnt : per_chunk;
+      hipError_t he = table_block(c, tabs * tw * 4, &dst);
+      if (he != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MBFT_ERR_NOMEM, "compact keys: out of device memory (teeth " + std::to_string(t) + ")");
+      }
+      if (tabs != cnt) {
+        c->teeth_chunk[t] = dst;
+        c->teeth_left[t] = tabs;
+      }
+    }
+    if (dst == c->teeth_chunk[t]) {
+      c->teeth_chunk[t] += tw * cnt;
+      c->teeth_left[t] -= cnt;
+    }
+  } else if (cls == (uint32_t)mbft_launch::kWindowNone) {
+    if (cnt <= c->tfree_left) {
+      dst = c->tfree_chunk;
+    } else {
+      // a block of its own for a large call, else a fresh chunk (what is
+      // left of the old one stays unused)
+      const size_t ents = cnt >= mbft_ctx::kTfreeChunk / 4 ? cnt : mbft_ctx::kTfreeChunk;
+      hipError_t he = table_block(c, ents * 64, &dst);
+      if (he != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MBFT_ERR_NOMEM, "table-free keys: out of device memory");
+      }
+      if (ents != cnt) {
+        c->tfree_chunk = dst;
+        c->tfree_left = ents;
+      }
+    }
+    if (dst == c->tfree_chunk) {
+      c->tfree_chunk += 16 * cnt;
+      c->tfree_left -= cnt;
+    }
+  } else {
+    hipError_t he = table_block(c, cnt * mbft_launch::table_words((int)cls) * sizeof(uint32_t), &dst);
+    if (he != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, MBFT_ERR_NOMEM, "key tables: out of device memory (window " + std::to_string(cls) + ")");
+    }
+  }
+  *out = dst;
+  return MBFT_OK;
+}
+
+// The data of cnt keys of class cls, one after another from dst, by the
+// class's builder; returns when it is built.
+int build_run(mbft_ctx* c, uint32_t cls, const uint32_t* words, size_t cnt, uint32_t* dst) {
+  HIPCHK(c, c->xy.ensure(64 * cnt));
+  HIPCHK(c, hipMemcpyAsync(c->xy.p, words, 64 * cnt, hipMemcpyHostToDevice, c->stream));
+  if (cls >= mbft::kTeethFlag) {
+    HIPCHK(c, mbft_launch::build_teeth_tables(c->xy.as<uint32_t>(), (int)cnt, (int)(cls & 0xFFu), dst, c->stream));
+  } else if (cls == (uint32_t)mbft_launch::kWindowNone) {
+    HIPCHK(c, mbft_launch::point_entries(c->xy.as<uint32_t>(), (int)cnt, dst, c->stream));
+  } else {
+    HIPCHK(c, c->bpts.ensure((size_t)mbft_launch::table_steps((int)cls) * 64 * cnt));
+    HIPCHK(c, mbft_launch::build_tables(c->xy.as<uint32_t>(), (int)cnt, (int)cls, c->bpts.as<uint32_t>(), dst,
+                                        c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MBFT_OK;
+}
+
+}  // namespace
+
+int place_keys(mbft_ctx* c, uint32_t cls, const uint32_t* words, size_t cnt, size_t max_reuse,
+               std::vector<uint32_t*>& pieces) {
+  const size_t tw = (size_t)(mbft::key_class_bytes(cls) / 4);
+  pieces.assign(cnt, nullptr);
+  size_t reused = 0;
+  while (reused < cnt && reused < max_reuse) {
+    const uintptr_t p = c->pieces.take(cls);
+    if (!p) break;
+    pieces[reused++] = reinterpret_cast<uint32_t*>(p);
+  }
+  size_t held = reused;  // pieces that go (back) on the list if a later step fails
+  auto undo = [&](int rc) {
+    for (size_t j = 0; j < held; j++) c->pieces.release(cls, reinterpret_cast<uintptr_t>(pieces[j]));
+    return rc;
+  };
+  if (reused < cnt) {
+    uint32_t* run = nullptr;
+    if (const int rc = fresh_run(c, cls, cnt - reused, &run)) return undo(rc);
+    for (size_t j = reused; j < cnt; j++) pieces[j] = run + (j - reused) * tw;
+    held = cnt;
+  }
+  // the reused pieces lie anywhere: their keys' data is built a group at a
+  // time -- one launch into a staging run of at most kStageMax bytes -- and
+  // copied out piece by piece; a class whose table fills the staging alone is
+  // built in place, a launch a piece
+  constexpr size_t kStageMax = (size_t)64 << 20;
+  const size_t group = kStageMax / (tw * 4) ? kStageMax / (tw * 4) : 1;
+  for (size_t j0 = 0; j0 < reused; j0 += group) {
+    const size_t g = reused - j0 < group ? reused - j0 : group;
+    if (g == 1) {
+      if (const int rc = build_run(c, cls, words + 16 * j0, 1, pieces[j0])) return undo(rc);
+      continue;
+    }
+    if (c->key_stage.ensure(g * tw * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      return undo(fail(c, MBFT_ERR_NOMEM, "key re-class: out of device memory (staging)"));
+    }
+    if (const int rc = build_run(c, cls, words + 16 * j0, g, c->key_stage.as<uint32_t>())) return undo(rc);
+    for (size_t j = 0; j < g; j++)
+      if (hipMemcpyAsync(pieces[j0 + j], c->key_stage.as<uint32_t>() + j * tw, tw * 4, hipMemcpyDeviceToDevice,
+                         c->stream) != hipSuccess)
+        return undo(fail(c, MBFT_ERR_HIP, "key re-class: copy out of staging"));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return undo(fail(c, MBFT_ERR_HIP, "key re-class: staging"));
+  }
+  if (reused < cnt)
+    if (const int rc = build_run(c, cls, words + 16 * reused, cnt - reused, pieces[reused])) return undo(rc);
+  return MBFT_OK;
+}
+
 // Register (dedup) raw points on ONE engine; validates on the GPU and builds
-// comb tables.
+// the keys' data in the current class.  New keys take the released slot
+// numbers first, lowest first, then fresh ones.
 int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t* out_slots,
                            uint8_t* valid_out) {
   std::vector<size_t> fresh;  // indices into input needing a new slot
   std::vector<uint32_t> slot_ids(n);
   std::map<std::array<uint8_t, 64>, uint32_t> pending;
+  const std::vector<uint32_t> freev = c->free_slots.lowest(n);  // what the new keys take first
+  const size_t nfree = freev.size();
   for (size_t i = 0; i < n; i++) {
     std::array<uint8_t, 64> k;
     memcpy(k.data(), xy64 + 64 * i, 64);
@@ -254,14 +402,14 @@ int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t*
       slot_ids[i] = pt->second;
       continue;
     }
-    const uint32_t sl = (uint32_t)(c->slots.size() + fresh.size());
+    const size_t f = fresh.size();
+    const uint32_t sl = f < nfree ? freev[f] : (uint32_t)(c->slots.size() + (f - nfree));
     pending[k] = sl;
     slot_ids[i] = sl;
     fresh.push_back(i);
   }
   if (!fresh.empty()) {
     const size_t m = fresh.size();
-    const size_t base = c->slots.size();
     std::vector<uint32_t> words(16 * m);
     for (size_t j = 0; j < m; j++) {
       const uint8_t* p = xy64 + 64 * fresh[j];
@@ -277,7 +425,8 @@ int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t*
     std::vector<uint32_t> ok(m);
     HIPCHK(c, hipMemcpyAsync(ok.data(), c->ok.p, m * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    // compact the valid points; their tables go into one new block
+    // compact the valid points
+    const uint32_t cls = key_class(c);
     std::vector<uint32_t> vwords;
     std::vector<uint32_t> vslots;
     for (size_t j = 0; j < m; j++) {
@@ -291,110 +440,37 @@ int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t*
         c->epoch_set.push_back(0);
       }
       si.fp_group = fg.first->second;
-      c->slots.push_back(si);
-      c->slot_of_xy[si.xy] = (uint32_t)(base + j);
-      c->keydesc.push_back(mbft::KeyDesc{nullptr, key_class(c), 0u});
+      const uint32_t sl = slot_ids[fresh[j]];
+      if (sl < c->slots.size()) {  // a released number (ascending: the list's lowest)
+        c->free_slots.take();
+        c->slots[sl] = si;
+        c->keydesc[sl] = mbft::KeyDesc{nullptr, cls, 0u};
+      } else {
+        c->slots.push_back(si);
+        c->keydesc.push_back(mbft::KeyDesc{nullptr, cls, 0u});
+      }
+      c->kd_dirty.mark(sl);
+      c->slot_of_xy[si.xy] = sl;
       if (si.valid) {
         vwords.insert(vwords.end(), &words[16 * j], &words[16 * j] + 16);
-        vslots.push_back((uint32_t)(base + j));
+        vslots.push_back(sl);
       }
     }
-    if (!vslots.empty() && c->q_teeth) {
-      // compact keys: a table of 2^t entries each, pooled per t like the
-      // table-free entries
-      const int t = c->q_teeth;
+    if (!vslots.empty()) {
+      // a call that brings a few keys takes released pieces of the class first;
+      // a many-key call takes one fresh run (one build launch)
+      constexpr size_t kReuseMaxKeys = 16;
       const size_t cnt = vslots.size();
-      const size_t tw = mbft_launch::teeth_table_words(t);
-      const size_t per_chunk = mbft_ctx::kTeethChunk / (tw * 4);
-      uint32_t* dst = nullptr;
-      if (cnt <= c->teeth_left[t]) {
-        dst = c->teeth_chunk[t];
-      } else {
-        const size_t tabs = cnt >= per_chunk / 4 ? cnt : per_chunk;
-        hipError_t he = table_block(c, tabs * tw * 4, &dst);
-        if (he != hipSuccess) {
-          // keep the slots (invalid) so slot numbering stays consistent
-          (void)hipGetLastError();
-          return fail(c, MBFT_ERR_NOMEM, "compact keys: out of device memory (teeth " +
-                                             std::to_string(t) + ")");
-        }
-        if (tabs != cnt) {
-          c->teeth_chunk[t] = dst;
-          c->teeth_left[t] = tabs;
-        }
-      }
-      if (dst == c->teeth_chunk[t]) {
-        c->teeth_chunk[t] += tw * cnt;
-        c->teeth_left[t] -= cnt;
-      }
-      HIPCHK(c, c->xy.ensure(64 * cnt));
-      HIPCHK(c, hipMemcpyAsync(c->xy.p, vwords.data(), 64 * cnt, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, mbft_launch::build_teeth_tables(c->xy.as<uint32_t>(), (int)cnt, t, dst, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      std::vector<uint32_t*> pcs;
+      // (on failure the slots stay, invalid, so slot numbering stays consistent)
+      if (const int rc = place_keys(c, cls, vwords.data(), cnt, cnt <= kReuseMaxKeys ? cnt : 0, pcs)) return rc;
       for (size_t j = 0; j < cnt; j++) {
         mbft::KeyDesc& kd = c->keydesc[vslots[j]];
-        kd.tab = dst + j * tw;
+        kd.tab = pcs[j];
         kd.valid = 1;
       }
-      c->tfree_keys += cnt;
-    } else if (!vslots.empty() && c->q_wbits == mbft_launch::kWindowNone) {
-      // table-free keys: each valid point as ONE comb entry, nothing else
-      const size_t cnt = vslots.size();
-      uint32_t* dst = nullptr;
-      if (cnt <= c->tfree_left) {
-        dst = c->tfree_chunk;
-      } else {
-        // a block of its own for a large call, else a fresh chunk (what is
-        // left of the old one stays unused)
-        const size_t ents = cnt >= mbft_ctx::kTfreeChunk / 4 ? cnt : mbft_ctx::kTfreeChunk;
-        hipError_t he = table_block(c, ents * 64, &dst);
-        if (he != hipSuccess) {
-          (void)hipGetLastError();
-          return fail(c, MBFT_ERR_NOMEM, "table-free keys: out of device memory");
-        }
-        if (ents != cnt) {
-          c->tfree_chunk = dst;
-          c->tfree_left = ents;
-        }
-      }
-      if (dst == c->tfree_chunk) {
-        c->tfree_chunk += 16 * cnt;
-        c->tfree_left -= cnt;
-      }
-      HIPCHK(c, c->xy.ensure(64 * cnt));
-      HIPCHK(c, hipMemcpyAsync(c->xy.p, vwords.data(), 64 * cnt, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, mbft_launch::point_entries(c->xy.as<uint32_t>(), (int)cnt, dst, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      for (size_t j = 0; j < cnt; j++) {
-        mbft::KeyDesc& kd = c->keydesc[vslots[j]];
-        kd.tab = dst + 16 * j;
-        kd.valid = 1;
-      }
-      c->tfree_keys += cnt;
-    } else if (!vslots.empty()) {
-      const int w = c->q_wbits;
-      const size_t cnt = vslots.size();
-      const size_t tw = mbft_launch::table_words(w);
-      uint32_t* blk = nullptr;
-      hipError_t he = table_block(c, cnt * tw * sizeof(uint32_t), &blk);
-      if (he != hipSuccess) {
-        // keep the slots (invalid) so slot numbering stays consistent
-        (void)hipGetLastError();
-        return fail(c, MBFT_ERR_NOMEM, "key tables: out of device memory (window " +
-                                           std::to_string(w) + ")");
-      }
-      HIPCHK(c, c->xy.ensure(16 * 4 * cnt));
-      HIPCHK(c, c->bpts.ensure((size_t)mbft_launch::table_steps(w) * 16 * 4 * cnt));
-      HIPCHK(c, hipMemcpyAsync(c->xy.p, vwords.data(), 16 * 4 * cnt, hipMemcpyHostToDevice,
-                               c->stream));
-      HIPCHK(c, mbft_launch::build_tables(c->xy.as<uint32_t>(), (int)cnt, w,
-                                          c->bpts.as<uint32_t>(), blk, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      for (size_t j = 0; j < cnt; j++) {
-        mbft::KeyDesc& kd = c->keydesc[vslots[j]];
-        kd.tab = blk + j * tw;
-        kd.valid = 1;
-      }
+      if (mbft::key_class_queued(cls)) c->tfree_keys += cnt;
+      c->live_bytes += cnt * mbft::key_class_bytes(cls);
     }
     int rc = upload_keydesc(c);
     if (rc) return rc;
@@ -424,10 +500,11 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
   // The batch's form, decided once: it sizes slowq[k] (the spill planes of
   // the grid that runs), names the s^-1 to run here and goes to the launcher.
   const mbft::InvSource src = mbft::verify_inv_source((long)n, lane_inv_max, d_winv != nullptr, d_count != nullptr);
-  const mbft::VerifyPlan plan =
+  const mbft::VerifyPlan plan = mbft::verify_plan_account(
       mbft::verify_plan((long)n, src, d_count != nullptr, /*has_planes_ws=*/!d_winv,
                         tb->split_max < 0 ? mbft_launch::split_max_env() : tb->split_max,
-                        tb->small_inv < 0 ? 2 : tb->small_inv);
+                        tb->small_inv < 0 ? 2 : tb->small_inv),
+      tb->accounting.load(std::memory_order_relaxed) && tb->d_uses != nullptr);
   HIPCHK(c, c->slowq[k].ensure(mbft::verify_slowq_words((long)n, plan) * 4));
   mbft_ctx::Ev ev{};
   if (c->prof) {
@@ -447,7 +524,7 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
                                       /*planes_ws=*/d_winv ? nullptr : c->winv[k].as<uint32_t>(), d_count,
                                       host_status};
     const mbft_launch::VerifyTables vt{tb->d_tabG, tb->g_wbits, tb->d_keys.as<mbft::KeyDesc>(),
-                                       (uint32_t)tb->slots.size(), tb->tfree_keys != 0};
+                                       (uint32_t)tb->slots.size(), tb->tfree_keys != 0, tb->d_uses, tb->d_rejects};
     HIPCHK(c, mbft_launch::verify(vb, vt, plan, st));
     HIPCHK(c, hipEventRecord(c->ev_done[k], st));
     if (c->prof) {
@@ -740,7 +817,7 @@ void mbft_ctx_destroy(mbft_ctx* c) {
                     &c->m_recs, &c->m_bytes, &c->m_chk, &c->m_flag, &c->m_cand, &c->m_chash,
                     &c->m_cslot, &c->m_uniq, &c->m_ref, &c->m_idx, &c->m_callof, &c->m_candof, &c->m_bounds,
                     &c->m_tkeys, &c->m_treps, &c->m_scan, &c->m_fpg, &c->m_info, &c->m_epset,
-                    &c->m_epval, &c->m_cap, &c->m_out, &c->b_bad, &c->m_pack})
+                    &c->m_epval, &c->m_cap, &c->m_out, &c->b_bad, &c->m_pack, &c->key_stage})
     b->release();
   for (PinnedBuf* b : {&c->h_e, &c->h_r, &c->h_s, &c->h_slot, &c->h_status, &c->h_udata, &c->h_uoff,
                        &c->h_uidx, &c->h_uep, &c->h_uctr, &c->h_desc, &c->h_small, &c->hm_small,
@@ -762,6 +839,8 @@ void mbft_ctx_destroy(mbft_ctx* c) {
   for (void* b : c->tab_blocks) hipFree(b);
   for (auto& b : c->free_blocks) hipFree(b.first);
   c->d_keys.release();
+  if (c->d_uses) hipFree(c->d_uses);
+  if (c->d_rejects) hipFree(c->d_rejects);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -875,8 +954,15 @@ int mbft_ctx_add_device(mbft_ctx* c, int device) {
   size_t a = 0;
   (void)hipSetDevice(device);
   while (a < ns) {
+    if (c->free_slots.holds((uint32_t)a)) {  // a released slot: the same hole on the peer
+      p->slots.push_back(c->slots[a]);
+      p->keydesc.push_back(mbft::KeyDesc{nullptr, c->keydesc[a].wbits, 0u});
+      p->kd_dirty.mark(a);
+      a++;  // (on the peer's free list once the replay is over: the keys after it keep their numbers)
+      continue;
+    }
     size_t b = a + 1;
-    while (b < ns && c->keydesc[b].wbits == c->keydesc[a].wbits) b++;
+    while (b < ns && c->keydesc[b].wbits == c->keydesc[a].wbits && !c->free_slots.holds((uint32_t)b)) b++;
     std::vector<uint8_t> xy(64 * (b - a));
     for (size_t j = a; j < b; j++) memcpy(&xy[64 * (j - a)], c->slots[j].xy.data(), 64);
     set_key_class(p, c->keydesc[a].wbits);
@@ -885,7 +971,13 @@ int mbft_ctx_add_device(mbft_ctx* c, int device) {
     a = b;
   }
   if (p->slots.size() != ns) return bail(MBFT_ERR_STATE, "peer slot mismatch");
+  for (uint32_t fs : c->free_slots.lowest(c->free_slots.size())) p->free_slots.release(fs);
+  if (const int urc = upload_keydesc(p)) return bail(urc, "peer engine: " + p->err);
   set_key_class(p, key_class(c));
+  if (c->accounting.load()) {
+    p->accounting.store(true);
+    if (const int grc = grow_key_counters(p)) return bail(grc, "peer engine: " + p->err);
+  }
   p->prof = false;
   p->split_max = c->split_max;
   p->small_inv = c->small_inv;
@@ -948,7 +1040,16 @@ int mbft_register_points(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t* o
   if (!c || (n && !xy64)) return MBFT_ERR_ARG;
   KeyWriteGuard g(c);
   if (hipSetDevice(c->device) != hipSuccess) return MBFT_ERR_HIP;
-  return register_points(c, xy64, n, out_slots, valid_out);
+  std::vector<uint32_t> got(n);
+  const int rc = register_points(c, xy64, n, got.data(), valid_out);
+  if (rc) return rc;
+  // slot numbers handed out raw stay the caller's until mbft_release_slots
+  if (c->slot_raw.size() < c->slots.size()) c->slot_raw.resize(c->slots.size(), 0);
+  for (size_t i = 0; i < n; i++) {
+    c->slot_raw[got[i]] = 1;
+    if (out_slots) out_slots[i] = got[i];
+  }
+  return MBFT_OK;
 }
 
 int mbft_set_public_key_xy(mbft_ctx* c, uint32_t role, uint32_t id, const uint8_t xy[64]) {
@@ -960,9 +1061,22 @@ int mbft_set_public_key_xy(mbft_ctx* c, uint32_t role, uint32_t id, const uint8_
   int rc = register_points(c, xy, 1, &slot, &valid);
   if (rc) return rc;
   if (!valid) return fail(c, MBFT_ERR_KEY, "x509: invalid elliptic curve public key");
-  c->roles[role][id] = KeyEntry{slot};
+  if (c->slot_refs.size() < c->slots.size()) c->slot_refs.resize(c->slots.size(), 0);
+  auto& ids = c->roles[role];
+  auto old = ids.find(id);
+  const bool had = old != ids.end();
+  const uint32_t was = had ? old->second.slot : 0;
+  if (had && was == slot) {  // the same key again
+    c->key_gen++;
+    return MBFT_OK;
+  }
+  if (had && was < c->slot_refs.size() && c->slot_refs[was]) c->slot_refs[was]--;
+  c->slot_refs[slot]++;
+  ids[id] = KeyEntry{slot};
   c->key_gen++;
-  return MBFT_OK;
+  // rotation by overwriting: the pair's earlier slot is released when nothing
+  // else uses it, under the rule of mbft_remove_public_key
+  return had ? release_if_unused(c, was) : MBFT_OK;
 }
 
 int mbft_set_public_key_pkix(mbft_ctx* c, uint32_t role, uint32_t id, const uint8_t* pkix,
@@ -1000,6 +1114,23 @@ int mbft_clear_keys(mbft_ctx* c) {
   c->slots.clear();
   c->slot_of_xy.clear();
   c->keydesc.clear();
+  // the released slot numbers and pieces go with the slots and the blocks; the
+  // use counts start again from zero
+  c->free_slots.clear();
+  c->pieces.clear();
+  c->kd_dirty.clear();
+  c->slot_refs.clear();
+  c->slot_raw.clear();
+  c->live_bytes = 0;
+  if (c->d_uses) {
+    HIPCHK(c, hipMemset(c->d_uses, 0, c->acct_slots * sizeof(uint64_t)));
+    HIPCHK(c, hipMemset(c->d_rejects, 0, c->acct_slots * sizeof(uint64_t)));
+  }
+  {
+    std::lock_guard<std::mutex> am(c->acct_mu);
+    c->res_uses.clear();
+    c->res_rejects.clear();
+  }
   for (auto& r : c->roles) r.second.clear();
   c->key_gen++;
   c->fp_group_of.clear();

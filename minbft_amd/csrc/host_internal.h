@@ -23,6 +23,7 @@
 #include "../../include/minbft_gpu.h"
 #include "env.h"
 #include "kernels.h"
+#include "key_plan.h"
 #include "sign_kernels.h"
 #include "sha256.h"
 
@@ -412,6 +413,34 @@ struct mbft_ctx {
   int q_teeth = 0;
   uint32_t* teeth_chunk[9] = {};
   size_t teeth_left[9] = {};
+  // The life of a key after registration (keys.cpp, key_plan.h; DESIGN.md
+  // §4.9), all under KeyWriteGuard.  Released slot numbers (free_slots) are
+  // taken first by the next registration, lowest first; released storage
+  // (pieces, one list per class) by later single registrations and re-classes
+  // of its class; kd_dirty: the keydesc entries changed since the last upload.
+  // slot_refs / slot_raw (the primary engine only): the (role, id) pairs that
+  // map to a slot, and whether mbft_register_points handed its number out.
+  // live_bytes: the key data of the valid slots.
+  mbft::SlotList free_slots;
+  mbft::PieceLists pieces;
+  mbft::DirtyRanges kd_dirty;
+  mbft_host::DevBuf key_stage;  // where the data of keys that take scattered pieces is built (place_keys)
+  std::vector<uint32_t> slot_refs;
+  std::vector<uint8_t> slot_raw;
+  uint64_t live_bytes = 0;
+  // Per-key use counts (mbft_set_key_accounting).  Off: no counter exists and
+  // no batch launches anything for them.  On: d_uses / d_rejects hold one
+  // uint64_t per slot on this table engine (acct_slots entries, grown and
+  // zero-filled with keydesc), added to by k_key_account at the end of every
+  // verify_device batch of this engine and its lanes; res_uses / res_rejects
+  // count the resident verifier's calls on the host (under acct_mu) and are
+  // merged when the counts are read.
+  std::atomic<bool> accounting{false};
+  uint64_t* d_uses = nullptr;
+  uint64_t* d_rejects = nullptr;
+  size_t acct_slots = 0;
+  std::mutex acct_mu;
+  std::vector<uint64_t> res_uses, res_rejects;
 
   // Multi-GPU in one process (mbft_ctx_add_device): peer engines on other
   // devices hold replicas of the comb tables (same slot numbering, same
@@ -704,6 +733,28 @@ int usig_single(mbft_ctx* c, const uint8_t* msg, size_t msg_len, uint8_t* tag_ou
 
 int register_points(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t* out_slots,
                     uint8_t* valid_out);
+// The key store's parts that keys.cpp (re-class, removal, use counts) shares
+// with registration (host.cpp), all on ONE engine, device set, under the
+// context's KeyWriteGuard.
+// upload_keydesc: the keydesc entries marked dirty go to the device, runs of
+// neighbours as one copy; everything after d_keys grew.  While accounting is on
+// it also grows the counters to the slots (grow_key_counters).
+int upload_keydesc(mbft_ctx* c);
+int grow_key_counters(mbft_ctx* c);
+uint32_t key_class(const mbft_ctx* c);
+void set_key_class(mbft_ctx* c, uint32_t cls);
+// Storage and data for cnt valid points (16 LE words each) in class cls:
+// pieces[j] receives key j's data address.  Up to max_reuse of them are taken
+// from the class's released pieces, the rest is ONE fresh run (a pooled chunk
+// or a block of its own, as registration always did).  Returns when the data
+// is built; on failure nothing is kept (taken pieces go back on their list).
+int place_keys(mbft_ctx* c, uint32_t cls, const uint32_t* words, size_t cnt, size_t max_reuse,
+               std::vector<uint32_t*>& pieces);
+// Slot sl is released (keys.cpp) if no (role, id) maps to it any more and its
+// number was not handed out raw; else nothing happens.
+int release_if_unused(mbft_ctx* c, uint32_t sl);
+// The resident verifier's calls while accounting is on (resident.cpp).
+void count_resident_use(mbft_ctx* c, uint32_t slot, uint8_t status);
 int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uint8_t* d_s,
                   const uint32_t* d_slot, size_t n, uint8_t* d_status, hipStream_t st,
                   bool host_status = false, bool latency = false,

@@ -242,7 +242,27 @@ struct VerifyTables {
   const KeyDesc* keys;
   uint32_t nslots;
   bool table_free;          // some key is of a class the comb does not serve (key_class_queued)
+  uint64_t* uses = nullptr;     // per-slot counters of the plan's use-count stage (nslots entries each;
+  uint64_t* rejects = nullptr;  // read only when plan.account is set)
 };
+// The use-count stage on its own (key_account.hip, k_key_account): per key slot
+// the batch's items under it (slot < nslots and KeyDesc.valid) and those of
+// them whose status is not MBFT_ACCEPT, ADDED into uses[] / rejects[].  Items
+// whose slot word is >= nslots (host-decided words, >= kHostSlot, among them)
+// or names an invalid slot are not counted.  ndev (optional): the item count on
+// the device, nothing past min(n, *ndev) is read.  verify() launches it last
+// where the plan says so.
+struct KeyAccount {
+  const uint32_t* slot;
+  const uint8_t* status;
+  long n;
+  const uint32_t* ndev;
+  const KeyDesc* keys;
+  uint32_t nslots;
+  uint64_t* uses;
+  uint64_t* rejects;
+};
+hipError_t key_account(const KeyAccount& a, hipStream_t st);
 // MBFT_SPLIT_MAX (default 256; 0 disables the split form), read once.
 long split_max_env();
 hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const mbft::VerifyPlan& plan, hipStream_t st);

@@ -3291,6 +3291,11 @@ hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const VerifyPlan&
       break;
     }
   }
+  if (plan.account) {
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return le;
+    return key_account(KeyAccount{b.slot, b.status, n, b.ndev, t.keys, t.nslots, t.uses, t.rejects}, st);
+  }
   return hipGetLastError();
 }
 

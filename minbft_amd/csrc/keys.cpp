@@ -1,0 +1,396 @@
+// The life of a key after registration: per-key use counts,
+// re-classing of registered keys by hand and by count, removal with reuse of
+// slot numbers and storage.  The decisions (free lists, the promotion choice)
+// are key_plan.h's; registration itself is host.cpp's.  Every entry point that
+// changes the key store holds KeyWriteGuard and replays the operation on the
+// peer engines in the same order, so slot numbers and classes keep agreeing.
+#include <algorithm>
+
+#include "host_internal.h"
+
+namespace mbft_host {
+
+// The table engines of a context: its own, then the peers'.
+static std::vector<mbft_ctx*> engines_of(mbft_ctx* c) {
+  std::vector<mbft_ctx*> e{c};
+  e.insert(e.end(), c->peers.begin(), c->peers.end());
+  return e;
+}
+
+// Everything that may still read old key data or add to the counters has
+// finished on the current device: the library's own batches are over
+// (KeyWriteGuard), the caller-stream entry points return before their kernels
+// do -- as mbft_clear_keys, the resident kernel parked first (the primary
+// engine has it), then the whole device.
+static int quiesce(mbft_ctx* c, mbft_ctx* e) {
+  if (e == c) resident_park(c);
+  HIPCHK(c, hipDeviceSynchronize());
+  return MBFT_OK;
+}
+
+// The counters follow the slots: grown (x1.5 at least) and zero-filled, the
+// counts so far carried over.  The adds of batches still in flight on caller
+// streams must land before the copy: the device is synchronized (growth only).
+int grow_key_counters(mbft_ctx* c) {
+  const size_t ns = c->keydesc.size();
+  if (c->d_uses && ns <= c->acct_slots) return MBFT_OK;
+  size_t cap = ns < 1024 ? 1024 : ns;
+  if (cap < c->acct_slots + c->acct_slots / 2) cap = c->acct_slots + c->acct_slots / 2;
+  uint64_t* nu = nullptr;
+  uint64_t* nr = nullptr;
+  if (hipMalloc(&nu, cap * sizeof(uint64_t)) != hipSuccess || hipMalloc(&nr, cap * sizeof(uint64_t)) != hipSuccess) {
+    (void)hipGetLastError();
+    if (nu) (void)hipFree(nu);
+    return fail(c, MBFT_ERR_NOMEM, "key use counts: out of device memory");
+  }
+  HIPCHK(c, hipMemsetAsync(nu, 0, cap * sizeof(uint64_t), c->stream));
+  HIPCHK(c, hipMemsetAsync(nr, 0, cap * sizeof(uint64_t), c->stream));
+  if (c->d_uses) {
+    if (c->res) resident_park(c);
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpyAsync(nu, c->d_uses, c->acct_slots * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nr, c->d_rejects, c->acct_slots * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->d_uses) (void)hipFree(c->d_uses);
+  if (c->d_rejects) (void)hipFree(c->d_rejects);
+  c->d_uses = nu;
+  c->d_rejects = nr;
+  c->acct_slots = cap;
+  return MBFT_OK;
+}
+
+void count_resident_use(mbft_ctx* c, uint32_t slot, uint8_t status) {
+  if (!c->accounting.load(std::memory_order_relaxed)) return;
+  if (slot >= c->keydesc.size() || !c->keydesc[slot].valid) return;
+  std::lock_guard<std::mutex> g(c->acct_mu);
+  if (c->res_uses.size() <= slot) {
+    c->res_uses.resize(c->keydesc.size(), 0);
+    c->res_rejects.resize(c->keydesc.size(), 0);
+  }
+  c->res_uses[slot]++;
+  if (status != MBFT_ACCEPT) c->res_rejects[slot]++;
+}
+
+namespace {
+
+// Every slot's counts summed over the engines and the resident counter
+// (caller holds KeyWriteGuard: no library batch is in flight; the streams the
+// library launches on are synchronized here).
+int read_usage(mbft_ctx* c, std::vector<uint64_t>& uses, std::vector<uint64_t>& rejects) {
+  const size_t ns = c->slots.size();
+  uses.assign(ns, 0);
+  rejects.assign(ns, 0);
+  std::vector<uint64_t> u(ns), r(ns);
+  for (mbft_ctx* e : engines_of(c)) {
+    if (!e->d_uses || ns == 0) continue;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    std::vector<mbft_ctx*> own{e};
+    for (mbft_ctx* l : c->lanes)
+      if (l->owner == e) own.push_back(l);
+    for (mbft_ctx* o : own)
+      for (hipStream_t st : {o->stream, o->vstream[0], o->vstream[1]})
+        if (st) HIPCHK(c, hipStreamSynchronize(st));
+    const size_t m = ns < e->acct_slots ? ns : e->acct_slots;
+    HIPCHK(c, hipMemcpyAsync(u.data(), e->d_uses, m * sizeof(uint64_t), hipMemcpyDeviceToHost, e->kstream));
+    HIPCHK(c, hipMemcpyAsync(r.data(), e->d_rejects, m * sizeof(uint64_t), hipMemcpyDeviceToHost, e->kstream));
+    HIPCHK(c, hipStreamSynchronize(e->kstream));
+    for (size_t i = 0; i < m; i++) {
+      uses[i] += u[i];
+      rejects[i] += r[i];
+    }
+  }
+  (void)hipSetDevice(c->device);
+  std::lock_guard<std::mutex> g(c->acct_mu);
+  for (size_t i = 0; i < c->res_uses.size() && i < ns; i++) {
+    uses[i] += c->res_uses[i];
+    rejects[i] += c->res_rejects[i];
+  }
+  return MBFT_OK;
+}
+
+// Slot sl's counters back to zero on every engine (a released slot).
+int zero_usage(mbft_ctx* c, uint32_t sl) {
+  for (mbft_ctx* e : engines_of(c)) {
+    if (!e->d_uses || sl >= e->acct_slots) continue;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    HIPCHK(c, hipMemsetAsync(e->d_uses + sl, 0, sizeof(uint64_t), e->stream));
+    HIPCHK(c, hipMemsetAsync(e->d_rejects + sl, 0, sizeof(uint64_t), e->stream));
+    HIPCHK(c, hipStreamSynchronize(e->stream));
+  }
+  (void)hipSetDevice(c->device);
+  std::lock_guard<std::mutex> g(c->acct_mu);
+  if (sl < c->res_uses.size()) c->res_uses[sl] = c->res_rejects[sl] = 0;
+  return MBFT_OK;
+}
+
+// Re-class on ONE engine (device set): the new data of every slot in `sl`
+// (valid, not yet in cls) is built first, then the descriptors are swapped
+// and uploaded, then -- once nothing can read the old data any more -- the old
+// storage goes on its class's piece list.  On any failure before the swap
+// every key keeps its class.
+int reclass_engine(mbft_ctx* c, mbft_ctx* e, const std::vector<uint32_t>& sl, uint32_t cls) {
+  const size_t cnt = sl.size();
+  if (cnt == 0) return MBFT_OK;
+  std::vector<uint32_t> words(16 * cnt);
+  for (size_t j = 0; j < cnt; j++) {
+    const uint8_t* p = e->slots[sl[j]].xy.data();
+    be_to_words(&words[16 * j], p);
+    be_to_words(&words[16 * j + 8], p + 32);
+  }
+  std::vector<uint32_t*> pcs;
+  if (const int rc = place_keys(e, cls, words.data(), cnt, cnt, pcs)) return e == c ? rc : fail(c, rc, "peer engine: " + e->err);
+  std::vector<mbft::KeyDesc> old(cnt);
+  for (size_t j = 0; j < cnt; j++) {
+    mbft::KeyDesc& kd = e->keydesc[sl[j]];
+    old[j] = kd;
+    kd.tab = pcs[j];
+    kd.wbits = cls;
+    e->kd_dirty.mark(sl[j]);
+  }
+  if (const int rc = upload_keydesc(e)) {
+    // the device may hold either descriptor of a slot, and both point at built
+    // data: the host goes back to the old ones (marked, so the next upload
+    // restores them on the device) and the new pieces stay out of use until
+    // the device has been synchronized -- they go on their list only then
+    for (size_t j = 0; j < cnt; j++) {
+      e->keydesc[sl[j]] = old[j];
+      e->kd_dirty.mark(sl[j]);
+    }
+    if (hipDeviceSynchronize() == hipSuccess && upload_keydesc(e) == MBFT_OK)
+      for (size_t j = 0; j < cnt; j++) e->pieces.release(cls, reinterpret_cast<uintptr_t>(pcs[j]));
+    return e == c ? rc : fail(c, rc, "peer engine: " + e->err);
+  }
+  // the swap is in force on the device: the bookkeeping follows it
+  for (size_t j = 0; j < cnt; j++) {
+    if (mbft::key_class_queued(old[j].wbits)) e->tfree_keys--;
+    e->live_bytes -= mbft::key_class_bytes(old[j].wbits);
+  }
+  if (mbft::key_class_queued(cls)) e->tfree_keys += cnt;
+  e->live_bytes += cnt * mbft::key_class_bytes(cls);
+  // (if the synchronize itself fails the device is lost; the old storage is
+  // then left off the lists rather than handed out while it may be read)
+  if (const int rc = quiesce(c, e)) return rc;
+  for (const auto& o : old) e->pieces.release(o.wbits, reinterpret_cast<uintptr_t>(o.tab));
+  return MBFT_OK;
+}
+
+// The slots of `in` that a re-class into cls has to touch: valid and in
+// another class, each once.
+std::vector<uint32_t> reclass_list(const mbft_ctx* c, const uint32_t* in, size_t n, uint32_t cls) {
+  std::vector<uint32_t> sl;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t s = in[i];
+    if (s < c->keydesc.size() && c->keydesc[s].valid && c->keydesc[s].wbits != cls) sl.push_back(s);
+  }
+  std::sort(sl.begin(), sl.end());
+  sl.erase(std::unique(sl.begin(), sl.end()), sl.end());
+  return sl;
+}
+
+int reclass(mbft_ctx* c, const std::vector<uint32_t>& sl, uint32_t cls) {
+  if (sl.empty()) return MBFT_OK;
+  int rc = MBFT_OK;
+  for (mbft_ctx* e : engines_of(c)) {
+    std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
+    if (e != c) g.lock();
+    if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    rc = reclass_engine(c, e, sl, cls);
+    if (rc) break;
+  }
+  (void)hipSetDevice(c->device);
+  c->key_gen++;
+  return rc;
+}
+
+bool slot_in_use(const mbft_ctx* c, uint32_t sl) {
+  return (sl < c->slot_refs.size() && c->slot_refs[sl] != 0) || (sl < c->slot_raw.size() && c->slot_raw[sl] != 0);
+}
+
+// The slots of `sl` have no user left: invalid on every engine, their storage
+// on the piece lists, their numbers on the free list, their counters zero.
+// One descriptor upload and one device synchronize an engine, however many.
+int release_slots(mbft_ctx* c, const std::vector<uint32_t>& sl) {
+  if (sl.empty()) return MBFT_OK;
+  for (mbft_ctx* e : engines_of(c)) {
+    std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
+    if (e != c) g.lock();
+    if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    std::vector<mbft::KeyDesc> was;
+    for (uint32_t s : sl) {
+      mbft::KeyDesc& kd = e->keydesc[s];
+      was.push_back(kd);
+      kd.tab = nullptr;
+      kd.valid = 0;
+      e->kd_dirty.mark(s);
+    }
+    if (const int rc = upload_keydesc(e)) return e == c ? rc : fail(c, rc, "peer engine: " + e->err);
+    if (const int rc = quiesce(c, e)) return rc;
+    for (size_t j = 0; j < sl.size(); j++) {
+      if (was[j].valid) {
+        if (mbft::key_class_queued(was[j].wbits)) e->tfree_keys--;
+        e->live_bytes -= mbft::key_class_bytes(was[j].wbits);
+        e->pieces.release(was[j].wbits, reinterpret_cast<uintptr_t>(was[j].tab));
+      }
+      e->slot_of_xy.erase(e->slots[sl[j]].xy);
+      e->slots[sl[j]].valid = false;
+      e->free_slots.release(sl[j]);
+    }
+  }
+  (void)hipSetDevice(c->device);
+  c->key_gen++;
+  for (uint32_t s : sl)
+    if (const int rc = zero_usage(c, s)) return rc;
+  return MBFT_OK;
+}
+
+
+}  // namespace
+
+int release_if_unused(mbft_ctx* c, uint32_t sl) {
+  if (sl >= c->slots.size() || slot_in_use(c, sl) || c->free_slots.holds(sl)) return MBFT_OK;
+  return release_slots(c, {sl});
+}
+
+}  // namespace mbft_host
+
+using namespace mbft_host;
+
+extern "C" {
+
+int mbft_set_key_accounting(mbft_ctx* c, int enabled) {
+  if (!c || c->owner) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  for (mbft_ctx* e : engines_of(c)) {
+    if (enabled) {
+      if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+      if (const int rc = grow_key_counters(e)) {
+        (void)hipSetDevice(c->device);
+        return e == c ? rc : fail(c, rc, "peer engine: " + e->err);
+      }
+    }
+    e->accounting.store(enabled != 0);
+  }
+  (void)hipSetDevice(c->device);
+  return MBFT_OK;
+}
+
+int mbft_key_usage(mbft_ctx* c, const uint32_t* slots, size_t n, uint64_t* uses_out, uint64_t* rejects_out) {
+  if (!c || c->owner) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  std::vector<uint64_t> u, r;
+  if (const int rc = read_usage(c, u, r)) return rc;
+  for (size_t i = 0; i < n; i++) {
+    const size_t s = slots ? slots[i] : i;
+    if (uses_out) uses_out[i] = s < u.size() ? u[s] : 0;
+    if (rejects_out) rejects_out[i] = s < r.size() ? r[s] : 0;
+  }
+  return MBFT_OK;
+}
+
+int mbft_reset_key_usage(mbft_ctx* c) {
+  if (!c || c->owner) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  for (mbft_ctx* e : engines_of(c)) {
+    if (!e->d_uses) continue;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    if (const int rc = quiesce(c, e)) return rc;  // adds still in flight belong to the old count
+    HIPCHK(c, hipMemset(e->d_uses, 0, e->acct_slots * sizeof(uint64_t)));
+    HIPCHK(c, hipMemset(e->d_rejects, 0, e->acct_slots * sizeof(uint64_t)));
+  }
+  (void)hipSetDevice(c->device);
+  std::lock_guard<std::mutex> am(c->acct_mu);
+  std::fill(c->res_uses.begin(), c->res_uses.end(), 0);
+  std::fill(c->res_rejects.begin(), c->res_rejects.end(), 0);
+  return MBFT_OK;
+}
+
+int mbft_get_key_class(const mbft_ctx* c, uint32_t role, uint32_t id, uint32_t* cls, uint64_t* table_bytes) {
+  if (!c) return MBFT_ERR_ARG;
+  const int sl = mbft_key_slot(c, role, id);
+  if (sl < 0) return sl;
+  if ((size_t)sl >= c->keydesc.size()) return MBFT_ERR_STATE;
+  const mbft::KeyDesc& kd = c->keydesc[(size_t)sl];
+  if (cls) *cls = kd.wbits;
+  if (table_bytes) *table_bytes = kd.valid ? mbft::key_class_bytes(kd.wbits) : 0;
+  return MBFT_OK;
+}
+
+int mbft_set_slot_classes(mbft_ctx* c, const uint32_t* slots, size_t n, uint32_t cls) {
+  if (!c || c->owner || (n && !slots) || !mbft::key_class_known(cls)) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  for (size_t i = 0; i < n; i++)
+    if (slots[i] >= c->keydesc.size()) return fail(c, MBFT_ERR_ARG, "mbft_set_slot_classes: no such slot");
+  return reclass(c, reclass_list(c, slots, n, cls), cls);
+}
+
+int mbft_set_key_class(mbft_ctx* c, uint32_t role, uint32_t id, uint32_t cls) {
+  if (!c || c->owner || !mbft::key_class_known(cls)) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  const int sl = mbft_key_slot(c, role, id);
+  if (sl < 0) return sl;
+  const uint32_t s = (uint32_t)sl;
+  if (s >= c->keydesc.size() || !c->keydesc[s].valid) return fail(c, MBFT_ERR_ARG, "mbft_set_key_class: invalid slot");
+  return reclass(c, reclass_list(c, &s, 1, cls), cls);
+}
+
+int mbft_promote_hot_keys(mbft_ctx* c, uint32_t cls, size_t max_keys, uint64_t min_uses, size_t* promoted) {
+  if (promoted) *promoted = 0;
+  if (!c || c->owner || !mbft::key_class_known(cls)) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  std::vector<uint64_t> u, r;
+  if (const int rc = read_usage(c, u, r)) return rc;
+  const size_t ns = c->keydesc.size();
+  std::vector<uint32_t> co(ns);
+  std::vector<uint8_t> valid(ns);
+  for (size_t i = 0; i < ns; i++) {
+    co[i] = c->keydesc[i].wbits;
+    valid[i] = c->keydesc[i].valid ? 1 : 0;
+  }
+  const std::vector<uint32_t> pick = mbft::promotion_choice(u.data(), co.data(), valid.data(), ns, cls, max_keys, min_uses);
+  const int rc = reclass(c, reclass_list(c, pick.data(), pick.size(), cls), cls);
+  if (rc == MBFT_OK && promoted) *promoted = pick.size();
+  return rc;
+}
+
+int mbft_remove_public_key(mbft_ctx* c, uint32_t role, uint32_t id) {
+  if (!c || c->owner) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  auto rs = c->roles.find(role);
+  if (rs == c->roles.end()) return MBFT_ERR_KEY;
+  auto it = rs->second.find(id);
+  if (it == rs->second.end()) return MBFT_ERR_KEY;
+  const uint32_t sl = it->second.slot;
+  rs->second.erase(it);
+  c->key_gen++;
+  if (sl < c->slot_refs.size() && c->slot_refs[sl]) c->slot_refs[sl]--;
+  return release_if_unused(c, sl);
+}
+
+int mbft_release_slots(mbft_ctx* c, const uint32_t* slots, size_t n) {
+  if (!c || c->owner || (n && !slots)) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  for (size_t i = 0; i < n; i++)
+    if (slots[i] >= c->slots.size()) return fail(c, MBFT_ERR_ARG, "mbft_release_slots: no such slot");
+  std::vector<uint32_t> gone;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t sl = slots[i];
+    if (sl < c->slot_raw.size()) c->slot_raw[sl] = 0;
+    if (!slot_in_use(c, sl) && !c->free_slots.holds(sl)) gone.push_back(sl);
+  }
+  std::sort(gone.begin(), gone.end());
+  gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
+  return release_slots(c, gone);
+}
+
+int mbft_key_memory(const mbft_ctx* c, uint64_t out[3]) {
+  if (!c || !out) return MBFT_ERR_ARG;
+  out[0] = c->live_bytes;
+  out[1] = c->pieces.bytes();
+  uint64_t blocks = 0;
+  for (size_t b : c->tab_sizes) blocks += b;
+  out[2] = blocks;
+  return MBFT_OK;
+}
+
+}  // extern "C"

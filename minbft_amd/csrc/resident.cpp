@@ -540,6 +540,7 @@ int resident_call(mbft_ctx* c, const mbft_item& it, uint8_t* st) {
 #endif
       g = host_join_check(loc, np, r);
     }
+    count_resident_use(c, key, g);  // (these calls never pass verify_device)
 #ifdef MBFT_SRV_TIMING
     const double tt4 = now_ms();
     {
@@ -649,6 +650,7 @@ int resident_check(mbft_ctx* c, const mbft_item* items, size_t n, uint8_t* gst,
       } else {
         gst[gpu[j]] = st[j];
       }
+    for (size_t j = 0; j < m; j++) count_resident_use(c, key[gpu[j]], gst[gpu[j]]);
     R->calls += m;
   }
   if (usig)

@@ -38,7 +38,23 @@ struct VerifyPlan {
   bool ninv_first;   // k_ninv_local<1> into the planes workspace runs first
   bool queue_reset;  // a memset resets the table-free queue's counter in front of the kernel (where
                      // a key of that class exists; the exact-path queue's: the s^-1 kernels)
+  bool account = false;  // k_key_account ends the batch: after the form's last kernel that writes a
+                         // status (kLarge: after k_verify_slow and k_verify_ladder)
 };
+
+// The per-key use counts (mbft_set_key_accounting): the stage is part of the
+// plan, off unless the context asks for it.
+constexpr VerifyPlan verify_plan_account(VerifyPlan p, bool accounting) {
+  p.account = accounting;
+  return p;
+}
+// Its grid: one item per lane, 256 a block, grid-stride past kAccountBpc blocks
+// per CU -- a wave carries its last slot's sums from one step to the next, so
+// fewer, longer waves mean fewer atomics on a hot key's counters.
+constexpr long kAccountBpc = 4;
+constexpr long key_account_blocks(long n, long ncu) {
+  return (n + 255) / 256 < ncu * kAccountBpc ? (n + 255) / 256 : ncu * kAccountBpc;
+}
 
 // split_max: 0 disables the split form.  small_form (0 .. 3,
 // mbft_set_small_batch_inverse) is the form past it: 0 lane pairs inverting
