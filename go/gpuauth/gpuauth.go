@@ -103,6 +103,15 @@ type Config struct {
 	// large client set (INTEGRATION.md).  Zero: not used.  It wins over
 	// ClientWindow and TableFreeClients; a value outside 2..8 fails New.
 	ClientTeeth int
+	// ClientSignedTeeth (2..9) registers client keys as SIGNED compact keys
+	// (mbft_set_key_signed_teeth): the compact class's comb over a signed
+	// recoding, whose table holds 2^(ClientSignedTeeth-1) entries of 64 bytes
+	// per key (128 B at 2, 1 KiB at 5, 16 KiB at 9) -- half the bytes of
+	// ClientTeeth at the same teeth, or one more tooth for the same bytes
+	// (INTEGRATION.md).  Zero: not used.  Exclusive with ClientTeeth and
+	// TableFreeClients: New fails when it is set beside either, and for a
+	// value outside 2..9.
+	ClientSignedTeeth int
 	// Private keys of the ECDSA roles this node signs as (CPU signing with
 	// the reference scheme, crypto.go:63-76), used when Generator is nil.
 	PrivateKeys map[api.AuthenticationRole]*ecdsa.PrivateKey
@@ -162,7 +171,7 @@ type Config struct {
 }
 
 // HotKeys is the promotion policy of Config.HotKeys.  Class is a key class
-// code: a comb window 4..29, or KeyClassTeeth(t).  A promotion costs one
+// code: a comb window 4..29, KeyClassTeeth(t) or KeyClassSignedTeeth(t).  A promotion costs one
 // device synchronize, so PromoteEvery should be hundreds of batches.
 type HotKeys struct {
 	PromoteEvery int
@@ -206,6 +215,9 @@ var ecdsaScheme = &authen.PublicAuthenScheme{HashScheme: crypto.SHA256, SigCiphe
 // (as loaded by LoadSimpleKeyStore, keymanager.go:179-227).
 func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnabled bool,
 	cfg Config) (*Authenticator, error) {
+	if cfg.ClientSignedTeeth != 0 && (cfg.ClientTeeth != 0 || cfg.TableFreeClients) {
+		return nil, fmt.Errorf("ClientSignedTeeth is exclusive with ClientTeeth and TableFreeClients")
+	}
 	devices := cfg.Devices
 	if len(devices) == 0 {
 		devices = []int{0}
@@ -241,7 +253,7 @@ func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnable
 			continue // no scheme for the role (authenticator.go:126-129): its calls are rejected anyway
 		}
 		if rc := setKeyClass(ctx, w, role); rc != C.MBFT_OK {
-			return fail("mbft_set_key_window / mbft_set_key_teeth", rc)
+			return fail("mbft_set_key_window / mbft_set_key_teeth / mbft_set_key_signed_teeth", rc)
 		}
 		C.mbft_add_role(ctx, C.uint32_t(role))
 		for id, pk := range m {
@@ -351,6 +363,7 @@ func KeysFromStore(ks PublicKeyStore, ids map[api.AuthenticationRole][]uint32) (
 type Windows struct {
 	Generator, Replica, USIG, Client int
 	ClientTeeth                      int
+	ClientSignedTeeth                int // != 0: signed compact client keys (Client is then 0)
 }
 
 // setKeyClass selects the class of the keys registered next for role: the
@@ -358,6 +371,9 @@ type Windows struct {
 func setKeyClass(ctx *C.mbft_ctx, w Windows, role api.AuthenticationRole) C.int {
 	switch role {
 	case api.ClientAuthen:
+		if w.ClientSignedTeeth != 0 {
+			return C.mbft_set_key_signed_teeth(ctx, C.int(w.ClientSignedTeeth))
+		}
 		if w.ClientTeeth != 0 {
 			return C.mbft_set_key_teeth(ctx, C.int(w.ClientTeeth))
 		}
@@ -375,7 +391,7 @@ func setKeyClass(ctx *C.mbft_ctx, w Windows, role api.AuthenticationRole) C.int 
 func DefaultWindows(nkeys map[api.AuthenticationRole]int, cfg Config) Windows {
 	var g, r, u, c C.int
 	nclients := nkeys[api.ClientAuthen]
-	if cfg.TableFreeClients || cfg.ClientTeeth != 0 {
+	if cfg.TableFreeClients || cfg.ClientTeeth != 0 || cfg.ClientSignedTeeth != 0 {
 		nclients = 0 // (compact tables are at most 16 KiB a key: left out of the plan)
 	}
 	C.mbft_plan_windows(C.int(firstDevice(cfg)), C.size_t(nkeys[api.ReplicaAuthen]),
@@ -392,6 +408,10 @@ func DefaultWindows(nkeys map[api.AuthenticationRole]int, cfg Config) Windows {
 	if cfg.ClientTeeth != 0 {
 		w.Client = int(C.MBFT_WINDOW_NONE) // what mbft_get_windows reports for the class
 		w.ClientTeeth = cfg.ClientTeeth
+	}
+	if cfg.ClientSignedTeeth != 0 {
+		w.Client = int(C.MBFT_WINDOW_NONE)
+		w.ClientSignedTeeth = cfg.ClientSignedTeeth
 	}
 	return w
 }

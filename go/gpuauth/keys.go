@@ -196,6 +196,10 @@ func (a *Authenticator) ensureKeys(calls []Call) {
 // (MBFT_KEY_CLASS_TEETH, a function-like macro cgo cannot call).
 func KeyClassTeeth(t int) uint32 { return 0x100 | uint32(t) }
 
+// KeyClassSignedTeeth is the class code of a signed compact key of t teeth
+// (MBFT_KEY_CLASS_SIGNED_TEETH): 2^(t-1) entries of 64 bytes, t in 2..9.
+func KeyClassSignedTeeth(t int) uint32 { return 0x200 | uint32(t) }
+
 // RemoveKey unmaps (role, id) (mbft_remove_public_key): its calls are then
 // rejected like those of an id never registered, and its slot and storage are
 // reused once nothing else maps to them.  With Config.KeyStore set the key is
@@ -213,7 +217,7 @@ func (a *Authenticator) RemoveKey(role api.AuthenticationRole, id uint32) error 
 
 // SetKeyClass rebuilds the verification data of the registered key
 // (role, id) in class cls: a comb window 4..29, MBFT_WINDOW_NONE or
-// KeyClassTeeth(t).  On failure the key keeps its class.  One device
+// KeyClassTeeth(t) or KeyClassSignedTeeth(t).  On failure the key keeps its class.  One device
 // synchronize a call.
 func (a *Authenticator) SetKeyClass(role api.AuthenticationRole, id uint32, cls uint32) error {
 	rc := C.mbft_set_key_class(a.ctx, C.uint32_t(roleByte(role)), C.uint32_t(id), C.uint32_t(cls))

@@ -221,14 +221,48 @@ int mbft_get_windows(const mbft_ctx* ctx, int* g_wbits, int* q_wbits);
 #define MBFT_TEETH_MAX 8
 int mbft_set_key_teeth(mbft_ctx* ctx, int teeth);        /* keys registered AFTER the call */
 int mbft_get_key_teeth(const mbft_ctx* ctx, int* teeth); /* 0 while the current class is a window */
+/* SIGNED COMPACT keys: the same comb over a signed all-nonzero recoding of
+ * u2, whose table holds only the entries with a positive top tooth: 2^(t-1)
+ * entries of 64 B for t teeth, half the compact table of the same t -- one
+ * more tooth for the same bytes.  mbft_set_key_signed_teeth(ctx, t), t in
+ * MBFT_STEETH_MIN .. MBFT_STEETH_MAX, gives keys registered AFTER the call
+ * this class.  Bytes per key and field reductions for u2 Q, counted from the
+ * formulas (doubling 8, mixed addition 10; the signed comb has no zero
+ * column, d - 1 doublings and d - 1 additions):
+ *   bytes/key   unsigned        signed         ratio
+ *   128 B       -- (ladder, 64 B: ~2,900)  s2: 2,286   new point
+ *   256 B       t2: ~1,980      s3: 1,530      0.77
+ *   512 B       t3: ~1,430      s4: 1,134      0.79
+ *   1 KiB       t4: ~1,100      s5:   918      0.83
+ *   2 KiB       t5:   ~912      s6:   756      0.83
+ *   4 KiB       t6:   ~760      s7:   648      0.85
+ *   8 KiB       t7:   ~655      s8:   558      0.85
+ *   16 KiB      t8:   ~570      s9:   504      0.88
+ * A million clients at 4 signed teeth take 512 MiB.  These are counts;
+ * measured, signed t runs in the time of unsigned t at half
+ * its bytes, and at equal bytes in 0.71 (s3 / t2) to 0.95 (s9 / t8) of the
+ * unsigned class's time: faster for every t.  Any other t is MBFT_ERR_ARG; MBFT_ERR_NOMEM at registration
+ * if the tables do not fit (the slots stay invalid).  mbft_set_key_teeth and
+ * mbft_set_key_window switch away from this class as they switch between
+ * each other.  While signed teeth are selected mbft_get_windows reports key
+ * window 0, mbft_get_key_teeth reports 0 and mbft_get_key_signed_teeth
+ * reports t (0 while another class is selected).  Every verify entry point
+ * serves such keys, side by side with every other class. */
+#define MBFT_STEETH_MIN 2
+#define MBFT_STEETH_MAX 9
+int mbft_set_key_signed_teeth(mbft_ctx* ctx, int teeth);        /* keys registered AFTER the call */
+int mbft_get_key_signed_teeth(const mbft_ctx* ctx, int* teeth); /* 0 unless this class is selected */
 /* THE LIFE OF A KEY AFTER REGISTRATION.  Every call below
  * that changes the key store waits for the library's batches in flight, like
  * registration, and is replayed on the peer engines (mbft_ctx_add_device).
  *
  * A key's CLASS has one code, the one its descriptor carries: a comb window
- * 4..29, MBFT_WINDOW_NONE (table-free), or MBFT_KEY_CLASS_TEETH(t) for a
- * compact key of t = MBFT_TEETH_MIN..MBFT_TEETH_MAX teeth.  Classes are ordered
- * by the bytes of one key's data (64 B, 64 B x 2^t, the comb table).
+ * 4..29, MBFT_WINDOW_NONE (table-free), MBFT_KEY_CLASS_TEETH(t) for a
+ * compact key of t = MBFT_TEETH_MIN..MBFT_TEETH_MAX teeth, or
+ * MBFT_KEY_CLASS_SIGNED_TEETH(t) for a signed compact key of t =
+ * MBFT_STEETH_MIN..MBFT_STEETH_MAX teeth.  Classes are ordered by the bytes
+ * of one key's data (64 B, 64 B x 2^t, 64 B x 2^(t-1), the comb table); a
+ * signed t and an unsigned t - 1 tie, and neither is promoted into the other.
  *
  * Use counts.  mbft_set_key_accounting(ctx, 1) (default off: nothing is
  * allocated, no batch launches anything more) makes every batch end with one
@@ -287,6 +321,7 @@ int mbft_get_key_teeth(const mbft_ctx* ctx, int* teeth); /* 0 while the current 
  *     pieces awaiting reuse, out[2] bytes of key blocks held, on the
  *     context's own engine. */
 #define MBFT_KEY_CLASS_TEETH(t) (0x100 | (t))
+#define MBFT_KEY_CLASS_SIGNED_TEETH(t) (0x200 | (t))
 int mbft_set_key_accounting(mbft_ctx* ctx, int enabled);
 int mbft_key_usage(mbft_ctx* ctx, const uint32_t* slots, size_t n, uint64_t* uses_out,
                    uint64_t* rejects_out);

@@ -46,11 +46,19 @@ ROLE_CLIENT = 3
 WINDOW_NONE = 0
 #: teeth of compact keys (MBFT_TEETH_MIN, MBFT_TEETH_MAX)
 TEETH_MIN, TEETH_MAX = 2, 8
+#: teeth of signed compact keys (MBFT_STEETH_MIN, MBFT_STEETH_MAX)
+STEETH_MIN, STEETH_MAX = 2, 9
 
 
 def key_class_teeth(t: int) -> int:
     """The class code of a compact key of t teeth (MBFT_KEY_CLASS_TEETH)."""
     return 0x100 | t
+
+
+def KEY_CLASS_SIGNED_TEETH(t: int) -> int:  # noqa: N802 (the header's macro name)
+    """The class code of a signed compact key of t teeth
+    (MBFT_KEY_CLASS_SIGNED_TEETH)."""
+    return 0x200 | t
 
 
 #: bytes per tag slot of the batch signer (MBFT_TAG_SLOT)
@@ -88,6 +96,7 @@ EXPORTED = [
     "mbft_usig_init", "mbft_usig_id", "mbft_usig_next_counter", "mbft_usig_create_uis_digests",
     "mbft_usig_create_uis_flat", "mbft_usig_sign_messages_flat",
     "mbft_set_key_teeth", "mbft_get_key_teeth",
+    "mbft_set_key_signed_teeth", "mbft_get_key_signed_teeth",
     "mbft_set_key_accounting", "mbft_key_usage", "mbft_reset_key_usage",
     "mbft_get_key_class", "mbft_set_key_class", "mbft_set_slot_classes", "mbft_promote_hot_keys",
     "mbft_remove_public_key", "mbft_release_slots", "mbft_key_memory",
@@ -241,6 +250,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_set_generator_window": (i, [vp, i]),
         "mbft_set_key_teeth": (i, [vp, i]),
         "mbft_get_key_teeth": (i, [vp, ctypes.POINTER(i)]),
+        "mbft_set_key_signed_teeth": (i, [vp, i]),
+        "mbft_get_key_signed_teeth": (i, [vp, ctypes.POINTER(i)]),
         "mbft_set_key_accounting": (i, [vp, i]),
         "mbft_key_usage": (i, [vp, vp, sz, vp, vp]),
         "mbft_reset_key_usage": (i, [vp]),

@@ -191,6 +191,21 @@ class Authenticator:
         self._check(self.lib.mbft_get_key_teeth(self.ctx, ctypes.byref(t)), "get_key_teeth")
         return t.value
 
+    def set_key_signed_teeth(self, teeth: int):
+        """Signed compact keys for keys registered after the call: a table of
+        ``2**(teeth - 1)`` entries of 64 bytes per key (``teeth`` in 2..9:
+        128 B to 16 KiB), half the compact table of the same teeth, verified
+        by the same comb over a signed all-nonzero recoding
+        (include/minbft_gpu.h lists the cost).  A later ``set_key_teeth`` or
+        ``set_key_window`` switches away."""
+        self._check(self.lib.mbft_set_key_signed_teeth(self.ctx, teeth), "set_key_signed_teeth")
+
+    def key_signed_teeth(self) -> int:
+        """Teeth of the signed compact class while it is selected, else 0."""
+        t = ctypes.c_int()
+        self._check(self.lib.mbft_get_key_signed_teeth(self.ctx, ctypes.byref(t)), "get_key_signed_teeth")
+        return t.value
+
     # -------------------------------------------- a key's life after registration
     def set_key_accounting(self, enabled: bool):
         """Per-key use counts on the GPU (off by default): while on, every
@@ -216,7 +231,8 @@ class Authenticator:
 
     def key_class(self, role: int, key_id: int) -> Tuple[int, int]:
         """(class code, bytes of key data) of a registered (role, id): a comb
-        window 4..29, 0 (table-free) or ``_lib.key_class_teeth(t)``."""
+        window 4..29, 0 (table-free), ``_lib.key_class_teeth(t)`` or
+        ``_lib.KEY_CLASS_SIGNED_TEETH(t)``."""
         cls, nb = ctypes.c_uint32(), ctypes.c_uint64()
         self._check(self.lib.mbft_get_key_class(self.ctx, role, key_id, ctypes.byref(cls), ctypes.byref(nb)),
                     "get_key_class")

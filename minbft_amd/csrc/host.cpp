@@ -240,12 +240,16 @@ uint64_t fingerprint_of(const uint8_t xy[64]) {
 }
 
 // The class of keys registered from now on as KeyDesc.wbits carries it: the
-// key window (0: table-free), or kTeethFlag | t for compact keys.
+// key window (0: table-free), kTeethFlag | t for compact keys, or
+// kSignedTeethFlag | t for signed compact keys.
 uint32_t key_class(const mbft_ctx* c) {
+  if (c->q_steeth) return mbft::kSignedTeethFlag | (uint32_t)c->q_steeth;
   return c->q_teeth ? (mbft::kTeethFlag | (uint32_t)c->q_teeth) : (uint32_t)c->q_wbits;
 }
 void set_key_class(mbft_ctx* c, uint32_t cls) {
-  c->q_teeth = cls >= mbft::kTeethFlag ? (int)(cls & 0xFFu) : 0;
+  const bool sg = cls >= mbft::kSignedTeethFlag;
+  c->q_steeth = sg ? (int)(cls & 0xFFu) : 0;
+  c->q_teeth = !sg && cls >= mbft::kTeethFlag ? (int)(cls & 0xFFu) : 0;
   c->q_wbits = cls >= mbft::kTeethFlag ? mbft_launch::kWindowNone : (int)cls;
 }
 
@@ -257,26 +261,31 @@ namespace {
 int fresh_run(mbft_ctx* c, uint32_t cls, size_t cnt, uint32_t** out) {
   uint32_t* dst = nullptr;
   if (cls >= mbft::kTeethFlag) {
+    // (the signed class pools the same way, in chunk lists of its own)
+    const bool sg = cls >= mbft::kSignedTeethFlag;
     const int t = (int)(cls & 0xFFu);
-    const size_t tw = mbft_launch::teeth_table_words(t);
+    const size_t tw = sg ? mbft_launch::steeth_table_words(t) : mbft_launch::teeth_table_words(t);
+    uint32_t*& chunk = sg ? c->steeth_chunk[t] : c->teeth_chunk[t];
+    size_t& left = sg ? c->steeth_left[t] : c->teeth_left[t];
     const size_t per_chunk = mbft_ctx::kTeethChunk / (tw * 4);
-    if (cnt <= c->teeth_left[t]) {
-      dst = c->teeth_chunk[t];
+    if (cnt <= left) {
+      dst = chunk;
     } else {
       const size_t tabs = cnt >= per_chunk / 4 ? cnt : per_chunk;
       hipError_t he = table_block(c, tabs * tw * 4, &dst);
       if (he != hipSuccess) {
         (void)hipGetLastError();
-        return fail(c, MBFT_ERR_NOMEM, "compact keys: out of device memory (teeth " + std::to_string(t) + ")");
+        return fail(c, MBFT_ERR_NOMEM, std::string(sg ? "signed compact" : "compact") +
+                                           " keys: out of device memory (teeth " + std::to_string(t) + ")");
       }
       if (tabs != cnt) {
-        c->teeth_chunk[t] = dst;
-        c->teeth_left[t] = tabs;
+        chunk = dst;
+        left = tabs;
       }
     }
-    if (dst == c->teeth_chunk[t]) {
-      c->teeth_chunk[t] += tw * cnt;
-      c->teeth_left[t] -= cnt;
+    if (dst == chunk) {
+      chunk += tw * cnt;
+      left -= cnt;
     }
   } else if (cls == (uint32_t)mbft_launch::kWindowNone) {
     if (cnt <= c->tfree_left) {
@@ -315,7 +324,9 @@ int fresh_run(mbft_ctx* c, uint32_t cls, size_t cnt, uint32_t** out) {
 int build_run(mbft_ctx* c, uint32_t cls, const uint32_t* words, size_t cnt, uint32_t* dst) {
   HIPCHK(c, c->xy.ensure(64 * cnt));
   HIPCHK(c, hipMemcpyAsync(c->xy.p, words, 64 * cnt, hipMemcpyHostToDevice, c->stream));
-  if (cls >= mbft::kTeethFlag) {
+  if (cls >= mbft::kSignedTeethFlag) {
+    HIPCHK(c, mbft_launch::build_steeth_tables(c->xy.as<uint32_t>(), (int)cnt, (int)(cls & 0xFFu), dst, c->stream));
+  } else if (cls >= mbft::kTeethFlag) {
     HIPCHK(c, mbft_launch::build_teeth_tables(c->xy.as<uint32_t>(), (int)cnt, (int)(cls & 0xFFu), dst, c->stream));
   } else if (cls == (uint32_t)mbft_launch::kWindowNone) {
     HIPCHK(c, mbft_launch::point_entries(c->xy.as<uint32_t>(), (int)cnt, dst, c->stream));
@@ -897,7 +908,8 @@ int mbft_set_key_window(mbft_ctx* c, int wbits) {
     return MBFT_ERR_ARG;
   KeyWriteGuard g(c);
   c->q_wbits = wbits;
-  c->q_teeth = 0;  // (back from the compact class, if it was selected)
+  c->q_teeth = 0;  // (back from the compact classes, if one was selected)
+  c->q_steeth = 0;
   return MBFT_OK;
 }
 
@@ -905,7 +917,23 @@ int mbft_set_key_teeth(mbft_ctx* c, int teeth) {
   if (!c || teeth < mbft_launch::kTeethMin || teeth > mbft_launch::kTeethMax) return MBFT_ERR_ARG;
   KeyWriteGuard g(c);
   c->q_teeth = teeth;
+  c->q_steeth = 0;
   c->q_wbits = mbft_launch::kWindowNone;  // what mbft_get_windows reports meanwhile
+  return MBFT_OK;
+}
+
+int mbft_set_key_signed_teeth(mbft_ctx* c, int teeth) {
+  if (!c || teeth < mbft_launch::kSteethMin || teeth > mbft_launch::kSteethMax) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  c->q_steeth = teeth;
+  c->q_teeth = 0;
+  c->q_wbits = mbft_launch::kWindowNone;  // what mbft_get_windows reports meanwhile
+  return MBFT_OK;
+}
+
+int mbft_get_key_signed_teeth(const mbft_ctx* c, int* teeth) {
+  if (!c) return MBFT_ERR_ARG;
+  if (teeth) *teeth = c->q_steeth;
   return MBFT_OK;
 }
 
@@ -1110,6 +1138,10 @@ int mbft_clear_keys(mbft_ctx* c) {
   for (int t = 0; t < 9; t++) {
     c->teeth_chunk[t] = nullptr;
     c->teeth_left[t] = 0;
+  }
+  for (int t = 0; t < 10; t++) {
+    c->steeth_chunk[t] = nullptr;
+    c->steeth_left[t] = 0;
   }
   c->slots.clear();
   c->slot_of_xy.clear();

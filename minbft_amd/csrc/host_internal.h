@@ -413,6 +413,13 @@ struct mbft_ctx {
   int q_teeth = 0;
   uint32_t* teeth_chunk[9] = {};
   size_t teeth_left[9] = {};
+  // Signed compact keys (mbft_set_key_signed_teeth): q_steeth != 0 selects
+  // the class (q_teeth and q_wbits are then 0).  Tables of 2^(t-1) entries,
+  // pooled like the unsigned ones, one chunk list per signed t = 2 .. 9;
+  // valid slots count into tfree_keys too.
+  int q_steeth = 0;
+  uint32_t* steeth_chunk[10] = {};
+  size_t steeth_left[10] = {};
   // The life of a key after registration (keys.cpp, key_plan.h; DESIGN.md
   // §4.9), all under KeyWriteGuard.  Released slot numbers (free_slots) are
   // taken first by the next registration, lowest first; released storage

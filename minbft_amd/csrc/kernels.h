@@ -19,6 +19,10 @@ struct KeyDesc {
   uint32_t valid;
 };
 constexpr uint32_t kTeethFlag = 0x100u;
+// A signed compact key (t = 2 .. 9 teeth, teeth_dev.h): tab is its table of
+// 2^(t-1) entries, wbits kSignedTeethFlag | t -- a class code like the
+// compact one's, queued like it (>= kTeethFlag).
+constexpr uint32_t kSignedTeethFlag = 0x200u;
 // The key classes that take no part in the comb: window 0 and the compact
 // class.  k_verify queues their items for k_verify_ladder, the small-batch
 // kernels serve them in place (verify_ladder_inline), the resident verifier
@@ -203,6 +207,12 @@ hipError_t build_tables(const uint32_t* xy, int npts, int wbits, uint32_t* bpts,
 constexpr int kTeethMin = 2, kTeethMax = 8;
 size_t teeth_table_words(int teeth);
 hipError_t build_teeth_tables(const uint32_t* xy, int npts, int teeth, uint32_t* tab, hipStream_t st);
+// The signed compact key class (teeth_dev.h): `teeth` in 2 .. 9, a table of
+// 2^(teeth - 1) entries of 16 words per key (every entry read) -- 128 B at 2
+// teeth, 1 KiB at 5, 16 KiB at 9.  Arguments as build_teeth_tables.
+constexpr int kSteethMin = 2, kSteethMax = 9;
+size_t steeth_table_words(int teeth);
+hipError_t build_steeth_tables(const uint32_t* xy, int npts, int teeth, uint32_t* tab, hipStream_t st);
 hipError_t generator_xy(uint32_t* xy16, hipStream_t st);
 size_t ninv_workspace_words(long n);
 // One launch, one root inversion per 2,048 items (k_ninv_block, per

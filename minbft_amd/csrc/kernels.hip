@@ -405,6 +405,110 @@ __global__ void __launch_bounds__(64) k_teeth_table(const uint32_t* __restrict__
   teeth_affine<false>(dst, scr, count, tl, ne, 1, ne - 1);
 }
 
+// A signed compact key's table (teeth_dev.h): 2^(t-1) entries, entry idx =
+// (2^((t-1) d) + sum_(j < t-1) sigma_j 2^(j d)) Q with sigma_j = +1 iff bit j
+// of idx is set.  One lane per key, with k_teeth_table's parked Z and
+// Montgomery's trick; scratch as there, two planes of 8 words per entry and
+// lane (as large as the tables):
+//  1. ONE chain of (t - 1) d dependent doublings from Q passes D_j = 2 B_j
+//     (j < t - 1) and B_(j+1) = 2^((j+1) d) Q: these 2 t - 2 <= 2^(t-1) points
+//     are parked in the entry slots 0 .. 2 t - 3 (D_j at j, B_j at t - 2 + j)
+//     and made affine with one inversion;
+//  2. the D_j move to the scratch's second plane (unused until step 4: 2^(t-2)
+//     >= t - 1 points fit), entry 0 = B_(t-1) - B_(t-2) - .. - B_0 is summed in
+//     registers (B_0 = Q) and only then written over slot 0;
+//  3. every other entry in ascending idx is the entry without idx's lowest
+//     set bit j, plus D_j;
+//  4. every entry made affine with one more inversion.
+// No addition is degenerate.  Step 2 adds -2^(j d) Q to a Q with a = 2^((t-1)
+// d) - sum_(j < j' < t-1) 2^(j' d): a is a positive multiple of 2^((j+1) d),
+// so a > 2^(j d) and a - 2^(j d) > 0; step 3 adds the EVEN 2^(j d + 1) Q to m Q
+// with m an ODD entry multiplier, so m != +-2^(j d + 1).  All of these and
+// their sums lie in [1, 2^234) and N > 2^255 is prime: none of a -+ b is 0
+// (mod N), no operand is infinity, and no doubling meets order 2.
+__global__ void __launch_bounds__(64) k_steeth_table(const uint32_t* __restrict__ xy, long first, long count,
+                                                     int t, uint32_t* __restrict__ scr,
+                                                     uint32_t* __restrict__ tab) {
+  const long tl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tl >= count) return;
+  const long pt = first + tl;
+  const int d = teeth_columns(t);
+  const long ne = 1L << (t - 1);
+  uint32_t* dst = tab + 16 * (pt * ne);
+  uint32_t wx[8], wy[8];
+  load_words8(wx, xy + 16 * pt);
+  load_words8(wy, xy + 16 * pt + 8);
+  fe qx, qy;
+  fe_from_words(qx, wx);
+  fe_from_words(qy, wy);
+  fe_to_mont(qx, qx);
+  fe_to_mont(qy, qy);
+  fe_canon(qx);
+  fe_canon(qy);
+  // 1. the doubling chain
+  {
+    jac a;
+    a.X = qx;
+    a.Y = qy;
+    fe_one_mont(a.Z);
+#pragma unroll 1
+    for (int j = 0; j < t - 1; j++) {
+      ec_dbl(a, a);
+      park_xy(dst + 16 * (long)j, a);  // D_j
+      teeth_park(scr, count, tl, j, a.Z);
+#pragma unroll 1
+      for (int k = 1; k < d; k++) ec_dbl(a, a);
+      park_xy(dst + 16 * (long)(t - 1 + j), a);  // B_(j+1)
+      teeth_park(scr, count, tl, t - 1 + j, a.Z);
+    }
+  }
+  teeth_affine<false>(dst, scr, count, tl, ne, 0, 2 * t - 3);
+  // 2. D_j to the second plane, entry 0
+#pragma unroll 1
+  for (int j = 0; j < t - 1; j++) {
+    fe x, y;
+    load_point(x, y, reinterpret_cast<const uint4*>(dst + 16 * (long)j));
+    teeth_park(scr, count, tl, ne + 2 * j, x);
+    teeth_park(scr, count, tl, ne + 2 * j + 1, y);
+  }
+  {
+    jac s;
+    load_point(s.X, s.Y, reinterpret_cast<const uint4*>(dst + 16 * (long)(2 * t - 3)));  // B_(t-1)
+    fe_one_mont(s.Z);
+#pragma unroll 1
+    for (int j = t - 2; j >= 0; j--) {
+      fe bx, by;
+      if (j > 0) {
+        load_point(bx, by, reinterpret_cast<const uint4*>(dst + 16 * (long)(t - 2 + j)));
+      } else {
+        bx = qx;
+        by = qy;
+      }
+      fe_neg(by, by);
+      ec_madd(s, s, bx, by);
+    }
+    park_xy(dst, s);
+    teeth_park(scr, count, tl, 0, s.Z);
+  }
+  // 3. the other entries
+#pragma unroll 1
+  for (long v = 1; v < ne; v++) {
+    const long low = v & -v;
+    const int j = __ffsll((long long)low) - 1;
+    jac s;
+    load_point(s.X, s.Y, reinterpret_cast<const uint4*>(dst + 16 * (v - low)));
+    teeth_unpark(s.Z, scr, count, tl, v - low);
+    fe bx, by;
+    teeth_unpark(bx, scr, count, tl, ne + 2 * j);
+    teeth_unpark(by, scr, count, tl, ne + 2 * j + 1);
+    ec_madd(s, s, bx, by);
+    park_xy(dst + 16 * v, s);
+    teeth_park(scr, count, tl, v, s.Z);
+  }
+  // 4. affine
+  teeth_affine<false>(dst, scr, count, tl, ne, 0, ne - 1);
+}
+
 // ---------------------------------------------------------------------------
 // Batched inversion mod N (Montgomery's trick).  Values are Montgomery-form
 // limbs stored as 9 planes of n uint32 (SoA, coalesced).  Level structure:
@@ -1345,10 +1449,11 @@ MBFT_DEV void verify_ladder_item(const VerifyArgs& A, long i) {
   bool inf = true;
   jac j;
   // by the key's class: a compact key's doubling comb over its own small
-  // table (teeth_dev.h), else the ladder over the point.  A wave that holds
-  // both classes runs both bodies in turn.
+  // table (teeth_dev.h; signed or not, one body), else the ladder over the
+  // point.  A wave that holds both classes runs both bodies in turn
+  // (DESIGN.md §4.8).
   if (kd.wbits >= kTeethFlag) {
-    teeth_mul(j, inf, U2, kd.tab, (int)(kd.wbits & 0xFFu));
+    teeth_mul(j, inf, U2, kd.tab, (int)(kd.wbits & 0xFFu), (kd.wbits & kSignedTeethFlag) != 0u);
   } else {
     fe qx, qy;
     load_point(qx, qy, reinterpret_cast<const uint4*>(kd.tab));
@@ -3034,6 +3139,32 @@ hipError_t build_teeth_tables(const uint32_t* xy, int npts, int teeth, uint32_t*
   for (long first = 0; first < npts; first += chunk) {
     const long cnt = npts - first < chunk ? npts - first : chunk;
     hipLaunchKernelGGL(k_teeth_table, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st, xy, first, cnt,
+                       teeth, scratch, tab);
+    e = hipGetLastError();
+    if (e != hipSuccess) break;
+  }
+  // the launches read the scratch until they finish
+  const hipError_t es = hipStreamSynchronize(st);
+  const hipError_t ef = hipFree(scratch);
+  return e != hipSuccess ? e : (es != hipSuccess ? es : ef);
+}
+
+size_t steeth_table_words(int teeth) { return ((size_t)1 << (teeth - 1)) * 16u; }
+
+hipError_t build_steeth_tables(const uint32_t* xy, int npts, int teeth, uint32_t* tab, hipStream_t st) {
+  if (npts <= 0) return hipSuccess;
+  if (teeth < kSteethMin || teeth > kSteethMax) return hipErrorInvalidValue;
+  // as build_teeth_tables: one lane per key, scratch as large as a launch's
+  // tables, within 64 MiB
+  const size_t per_key = steeth_table_words(teeth) * 4;
+  long chunk = (long)(((size_t)64 << 20) / per_key);
+  if (chunk > npts) chunk = npts;
+  uint32_t* scratch = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&scratch), (size_t)chunk * per_key);
+  if (e != hipSuccess) return e;
+  for (long first = 0; first < npts; first += chunk) {
+    const long cnt = npts - first < chunk ? npts - first : chunk;
+    hipLaunchKernelGGL(k_steeth_table, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st, xy, first, cnt,
                        teeth, scratch, tab);
     e = hipGetLastError();
     if (e != hipSuccess) break;

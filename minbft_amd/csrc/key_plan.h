@@ -18,15 +18,19 @@ namespace mbft {
 
 // A key class as KeyDesc.wbits carries it (the public code of
 // mbft_set_key_class): a comb window 4 .. 29, 0 (table-free), or
-// 0x100 | t for a compact key of t = 2 .. 8 teeth.
+// 0x100 | t for a compact key of t = 2 .. 8 teeth, or 0x200 | t for a signed
+// compact key of t = 2 .. 9 teeth.
 constexpr uint32_t kClassTeeth = 0x100u;
+constexpr uint32_t kClassSignedTeeth = 0x200u;
 constexpr bool key_class_known(uint32_t cls) {
-  return cls == 0u || (cls >= 4u && cls <= 29u) || (cls >= (kClassTeeth | 2u) && cls <= (kClassTeeth | 8u));
+  return cls == 0u || (cls >= 4u && cls <= 29u) || (cls >= (kClassTeeth | 2u) && cls <= (kClassTeeth | 8u)) ||
+         (cls >= (kClassSignedTeeth | 2u) && cls <= (kClassSignedTeeth | 9u));
 }
 // Bytes of one key's verification data in class cls (64 B an entry): the
 // order of the classes wherever one is "cheaper" than another.
 constexpr uint64_t key_class_bytes(uint32_t cls) {
   if (cls == 0u) return 64u;
+  if (cls >= kClassSignedTeeth) return (uint64_t)64u << ((cls & 0xFFu) - 1u);  // 2^(t-1) entries
   if (cls >= kClassTeeth) return (uint64_t)64u << (cls & 0xFFu);
   const uint32_t w = cls, S = (256u + w - 1u) / w;
   return 64u * (((uint64_t)(S - 1u) << (w - 1u)) + ((uint64_t)1u << (256u - (S - 1u) * w)));
