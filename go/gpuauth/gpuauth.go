@@ -168,6 +168,31 @@ type Config struct {
 	// (mbft_promote_hot_keys; keys.go).  Off by default: nothing is counted
 	// and no key changes class on its own.
 	HotKeys HotKeys
+	// KeyBudget, if Every > 0, turns the per-key use counts on, sets the key
+	// memory budget (mbft_set_key_budget) and, every Every batches (counted as
+	// HotKeys counts them), rebalances the keys over Ladder within it, ages the counts
+	// and evicts cold client keys (mbft_rebalance_keys, mbft_age_key_usage,
+	// mbft_cold_keys; keys.go).  Off by default.
+	KeyBudget KeyBudget
+}
+
+// KeyBudget is the policy of Config.KeyBudget.  Bytes: the live key data per
+// engine the rebalance plans against.  Ladder: the key classes a key may be
+// given, cheapest in memory first (1..8 codes; include/minbft_gpu.h has the
+// rule they must pass).  AgeShift: after a rebalance every use count is
+// shifted right by so many bits (0: counts never fade).  MinUses: keys with
+// fewer uses stay at the first rung.  EvictMaxUses, if not 0: after the
+// ageing, the client keys with FEWER uses than this are removed (at most
+// 4096 a tick); with Config.KeyStore set they come back on their next call.  A
+// tick costs a device synchronize per class that changes, so Every should be
+// hundreds of batches.
+type KeyBudget struct {
+	Bytes        uint64
+	Ladder       []uint32
+	Every        int
+	AgeShift     uint
+	MinUses      uint64
+	EvictMaxUses uint64
 }
 
 // HotKeys is the promotion policy of Config.HotKeys.  Class is a key class
@@ -196,6 +221,9 @@ type Authenticator struct {
 	hot        HotKeys      // Config.HotKeys
 	batches    uint64       // VerifyBatch and CheckMessages batches so far (atomic; the promotion's clock)
 	promoteErr atomic.Value // string: the last promotion's failure, "" after one that worked
+	budget     KeyBudget    // Config.KeyBudget
+	rebalTicks uint64       // batches so far, the rebalance's clock (atomic)
+	rebalErr   atomic.Value // string: the last rebalance tick's failure, "" after one that worked
 
 	arenas arenaPool   // batches are marshalled here (library page-locked memory)
 	keys   keyRegistry // the (role, id) pairs the context holds (keys.go)
@@ -314,6 +342,15 @@ func New(keys map[api.AuthenticationRole]map[uint32]*ecdsa.PublicKey, usigEnable
 			return fail("mbft_set_key_accounting", rc)
 		}
 		a.hot = cfg.HotKeys
+	}
+	if cfg.KeyBudget.Every > 0 {
+		if rc := C.mbft_set_key_accounting(ctx, 1); rc != C.MBFT_OK {
+			return fail("mbft_set_key_accounting", rc)
+		}
+		if rc := C.mbft_set_key_budget(ctx, C.uint64_t(cfg.KeyBudget.Bytes)); rc != C.MBFT_OK {
+			return fail("mbft_set_key_budget", rc)
+		}
+		a.budget = cfg.KeyBudget
 	}
 	return a, nil
 }
@@ -483,6 +520,7 @@ func (a *Authenticator) VerifyBatch(calls []Call) []error {
 		if n == 1 {
 			out[0] = a.VerifyMessageAuthenTag(calls[0].Role, calls[0].ID, calls[0].Msg, calls[0].Tag)
 			a.promoteTick()
+			a.rebalanceTick()
 			return out
 		}
 		copy(out, a.VerifyBatch(calls[:n/2]))
@@ -509,6 +547,7 @@ func (a *Authenticator) VerifyBatch(calls []Call) []error {
 		out[i] = a.statusToErr(calls[i].Role, calls[i].ID, int(st[i]))
 	}
 	a.promoteTick()
+	a.rebalanceTick()
 	return out
 }
 

@@ -20,7 +20,11 @@ package gpuauth
 //   - RemoveKey, SetKeyClass, KeyUsage and PromoteHotKeys are the life of a
 //     key after that (include/minbft_gpu.h): a client that left gives its
 //     slot and table back, a hot key gets a table.  A removed key that the
-//     store still has comes back through ensureKey on its next call.
+//     store still has comes back through ensureKey on its next call;
+//   - SetKeyBudget, RebalanceKeys, AgeKeyUsage and ColdKeys keep that life
+//     within a memory budget (Config.KeyBudget runs them on a clock): cold
+//     keys lose their tables and hot ones gain them, counts fade, and client
+//     keys nobody uses are evicted.
 
 /*
 #include "minbft_gpu.h"
@@ -276,6 +280,145 @@ func (a *Authenticator) promoteTick() {
 // promotion, nil if it worked or none has run yet.
 func (a *Authenticator) LastPromoteError() error {
 	if s, ok := a.promoteErr.Load().(string); ok && s != "" {
+		return fmt.Errorf("%s", s)
+	}
+	return nil
+}
+
+// RebalanceResult is what a rebalance did (mbft_rebalance_result).
+type RebalanceResult struct {
+	LiveBefore, LiveAfter uint64 // bytes of live key data
+	PinnedBytes           uint64 // valid keys outside the ladder
+	OverBudget            uint64 // bytes past the budget with every ladder key at the first rung
+	Promoted, Demoted     int
+	KeysPerRung           []int // afterwards, one entry per rung of the ladder
+}
+
+// SetKeyBudget sets the bytes of live key data per engine a rebalance plans
+// against (mbft_set_key_budget); 0 is none.
+func (a *Authenticator) SetKeyBudget(bytes uint64) error {
+	if rc := C.mbft_set_key_budget(a.ctx, C.uint64_t(bytes)); rc != C.MBFT_OK {
+		return a.failure("mbft_set_key_budget", int(rc))
+	}
+	return nil
+}
+
+// RebalanceKeys gives every key whose class is a rung of ladder the rung of
+// its use count within the budget (mbft_rebalance_keys): it demotes and
+// promotes.  After a failure part way the result says what was done.
+func (a *Authenticator) RebalanceKeys(ladder []uint32, minUses uint64) (RebalanceResult, error) {
+	var res C.mbft_rebalance_result
+	lad := make([]C.uint32_t, len(ladder)+1) // (+1: an empty ladder still has an address)
+	for i, c := range ladder {
+		lad[i] = C.uint32_t(c)
+	}
+	rc := C.mbft_rebalance_keys(a.ctx, &lad[0], C.size_t(len(ladder)), C.uint64_t(minUses), &res)
+	out := RebalanceResult{LiveBefore: uint64(res.live_before), LiveAfter: uint64(res.live_after),
+		PinnedBytes: uint64(res.pinned_bytes), OverBudget: uint64(res.over_budget),
+		Promoted: int(res.promoted), Demoted: int(res.demoted)}
+	for i := 0; i < len(ladder) && i < len(res.keys_per_rung); i++ {
+		out.KeysPerRung = append(out.KeysPerRung, int(res.keys_per_rung[i]))
+	}
+	if rc != C.MBFT_OK {
+		return out, a.failure("mbft_rebalance_keys", int(rc))
+	}
+	return out, nil
+}
+
+// AgeKeyUsage shifts every use count right by shift bits (mbft_age_key_usage).
+func (a *Authenticator) AgeKeyUsage(shift uint) error {
+	if rc := C.mbft_age_key_usage(a.ctx, C.uint(shift)); rc != C.MBFT_OK {
+		return a.failure("mbft_age_key_usage", int(rc))
+	}
+	return nil
+}
+
+// ColdKeys returns the lowest max key slots whose summed uses are <= maxUses,
+// ascending, and how many such slots there are in all (mbft_cold_keys).
+func (a *Authenticator) ColdKeys(maxUses uint64, max int) ([]uint32, int, error) {
+	if max < 0 {
+		max = 0
+	}
+	buf := make([]C.uint32_t, max+1)
+	var n C.size_t
+	if rc := C.mbft_cold_keys(a.ctx, C.uint64_t(maxUses), &buf[0], C.size_t(max), &n); rc != C.MBFT_OK {
+		return nil, 0, a.failure("mbft_cold_keys", int(rc))
+	}
+	got := int(n)
+	if got > max {
+		got = max
+	}
+	out := make([]uint32, got)
+	for i := range out {
+		out[i] = uint32(buf[i])
+	}
+	return out, int(n), nil
+}
+
+// evictBatch bounds the client keys one rebalance tick removes.
+const evictBatch = 4096
+
+// evictCold removes the client keys the registry maps among the cold slots
+// (fewer than Config.KeyBudget.EvictMaxUses uses).  With Config.KeyStore set
+// such a key comes back through ensureKey on its next call.
+func (a *Authenticator) evictCold() error {
+	cold, _, err := a.ColdKeys(a.budget.EvictMaxUses-1, evictBatch)
+	if err != nil || len(cold) == 0 {
+		return err
+	}
+	a.keys.mu.RLock()
+	var gone []uint32
+	for k := range a.keys.known {
+		if k.role != api.ClientAuthen {
+			continue
+		}
+		slot := C.mbft_key_slot(a.ctx, C.uint32_t(roleByte(k.role)), C.uint32_t(k.id))
+		if slot < 0 {
+			continue
+		}
+		i := sort.Search(len(cold), func(i int) bool { return cold[i] >= uint32(slot) })
+		if i < len(cold) && cold[i] == uint32(slot) {
+			gone = append(gone, k.id)
+		}
+	}
+	a.keys.mu.RUnlock()
+	for _, id := range gone {
+		if err := a.RemoveKey(api.ClientAuthen, id); err != nil {
+			return err
+		}
+	}
+	return nil
+}
+
+// rebalanceTick counts a batch (VerifyBatch, CheckMessages) and, every
+// Config.KeyBudget.Every of them, rebalances the keys within the budget,
+// then ages the use counts, then evicts cold client keys.  A failure ends the
+// tick; its error is kept for LastRebalanceError.
+func (a *Authenticator) rebalanceTick() {
+	if a.budget.Every <= 0 {
+		return
+	}
+	if atomic.AddUint64(&a.rebalTicks, 1)%uint64(a.budget.Every) != 0 {
+		return
+	}
+	_, err := a.RebalanceKeys(a.budget.Ladder, a.budget.MinUses)
+	if err == nil && a.budget.AgeShift > 0 {
+		err = a.AgeKeyUsage(a.budget.AgeShift)
+	}
+	if err == nil && a.budget.EvictMaxUses > 0 {
+		err = a.evictCold()
+	}
+	if err != nil {
+		a.rebalErr.Store(err.Error())
+	} else {
+		a.rebalErr.Store("")
+	}
+}
+
+// LastRebalanceError reports the failure of the most recent Config.KeyBudget
+// tick, nil if it worked or none has run yet.
+func (a *Authenticator) LastRebalanceError() error {
+	if s, ok := a.rebalErr.Load().(string); ok && s != "" {
 		return fmt.Errorf("%s", s)
 	}
 	return nil

@@ -68,6 +68,8 @@ func (a *Authenticator) CheckMessages(msgs []api.AuthenMessage, n uint32) (api.C
 			client: m.ClientID, view: m.View}
 	}
 	a.promoteTick() // (a re-class keeps slots and statuses: the unresolved batch is unaffected)
+	// (so is it by an eviction: its statuses are taken, and only client keys leave)
+	a.rebalanceTick()
 	return mb, nil
 }
 

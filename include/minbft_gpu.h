@@ -335,6 +335,65 @@ int mbft_promote_hot_keys(mbft_ctx* ctx, uint32_t cls, size_t max_keys, uint64_t
 int mbft_remove_public_key(mbft_ctx* ctx, uint32_t role, uint32_t id);
 int mbft_release_slots(mbft_ctx* ctx, const uint32_t* slots, size_t n);
 int mbft_key_memory(const mbft_ctx* ctx, uint64_t out[3]);
+/* THE KEY MEMORY BUDGET.  The calls below follow the rules
+ * above: they wait for the library's batches in flight, are replayed on the
+ * peer engines, synchronize the library's own streams before the counters are
+ * read, and count work on a caller's own stream once that stream has finished.
+ * With no budget set and none of them called nothing is allocated or launched.
+ *   mbft_age_key_usage: every counter of every engine, and the resident
+ *     verifier's counts, shifted right by `shift` bits, so that old use fades.
+ *     0 does nothing; >= 64 is MBFT_ERR_ARG.  Each engine's counter is shifted
+ *     on its own: with P of them a slot's sum lands in
+ *     [(total >> shift) - (P - 1), total >> shift].
+ *   mbft_set_key_budget / mbft_get_key_budget: the bytes of LIVE KEY DATA PER
+ *     ENGINE (mbft_key_memory's out[0]) that mbft_rebalance_keys plans
+ *     against; 0, the default, is none.  Registration is never refused for the
+ *     budget's sake.
+ *   mbft_key_class_cost: the MODELLED field reductions of u2 Q under a key of
+ *     class cls -- 10 ceil(256 / W) for a comb window W, 2,908 table-free,
+ *     18 ceil(256 / t) - 8 for t teeth, signed or not; a model, not a
+ *     measurement.  0 for an unknown code.
+ *   mbft_rebalance_keys: gives every key whose class is a rung of `ladder` the
+ *     rung of its use count, so that the modelled verify cost is lowest within
+ *     the budget; it demotes and promotes.  `ladder`: 1 .. 8 class codes,
+ *     bytes strictly ascending, cost strictly descending, the gain per byte of
+ *     each step strictly decreasing (a dominated or non-convex rung is
+ *     MBFT_ERR_ARG).  The plan: every ladder key starts at rung 0; keys are
+ *     binned by use count (exact below 16, then eight bins an octave) and a
+ *     whole bin moves up one rung at a time, the steps taken in descending
+ *     order of (the bin's least count) x (reductions saved per byte) while the
+ *     bytes fit, stopping at the first step that does not fit; bins whose least
+ *     count is below max(min_uses, 1) stay at rung 0.  The budget may be left
+ *     unused by less than that step's bytes.  Valid keys of any other class are
+ *     PINNED: they keep their class and their bytes count against the budget.
+ *     Demotions are applied first, one bulk re-class per target rung from rung
+ *     0 upwards, then promotions from the top rung downwards, which reuse the
+ *     storage the demotions released; each non-empty bulk step costs one device
+ *     synchronize per engine.  A failure (MBFT_ERR_NOMEM, ...) stops the walk:
+ *     every bulk step is all or nothing, keys not yet moved keep their class,
+ *     *out reports what was done.  Where even rung 0 for every ladder key
+ *     exceeds the budget that plan is applied all the same and the call
+ *     returns MBFT_OK with over_budget set.  Use counts are kept.
+ *     MBFT_ERR_STATE: accounting is off (all-zero counts would demote every
+ *     key), or no budget is set.
+ *   mbft_cold_keys: the valid slots, of any class, whose summed uses are <=
+ *     max_uses, ascending -- the `cap` lowest when there are more -- and in
+ *     *count how many there are in all.  It changes nothing: eviction stays
+ *     the caller's (mbft_remove_public_key, mbft_release_slots). */
+typedef struct mbft_rebalance_result {
+  uint64_t live_before, live_after; /* mbft_key_memory's out[0] */
+  uint64_t pinned_bytes;            /* valid keys outside the ladder */
+  uint64_t over_budget;             /* bytes past the budget with every ladder key at rung 0, else 0 */
+  uint32_t promoted, demoted;       /* keys moved up / down */
+  uint32_t keys_per_rung[8];        /* afterwards */
+} mbft_rebalance_result;
+int mbft_age_key_usage(mbft_ctx* ctx, unsigned shift);
+int mbft_set_key_budget(mbft_ctx* ctx, uint64_t bytes);
+int mbft_get_key_budget(const mbft_ctx* ctx, uint64_t* bytes);
+uint32_t mbft_key_class_cost(uint32_t cls);
+int mbft_rebalance_keys(mbft_ctx* ctx, const uint32_t* ladder, size_t nladder, uint64_t min_uses,
+                        mbft_rebalance_result* out);
+int mbft_cold_keys(mbft_ctx* ctx, uint64_t max_uses, uint32_t* slots_out, size_t cap, size_t* count);
 /* USIG scheme present (authenticator.go:102-110: absent without a USIG). */
 int mbft_enable_usig(mbft_ctx* ctx, int enabled);
 /* Private key for GenerateMessageAuthenTag in an ECDSA role. */

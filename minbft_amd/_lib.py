@@ -100,7 +100,11 @@ EXPORTED = [
     "mbft_set_key_accounting", "mbft_key_usage", "mbft_reset_key_usage",
     "mbft_get_key_class", "mbft_set_key_class", "mbft_set_slot_classes", "mbft_promote_hot_keys",
     "mbft_remove_public_key", "mbft_release_slots", "mbft_key_memory",
+    "mbft_age_key_usage", "mbft_set_key_budget", "mbft_get_key_budget",
+    "mbft_rebalance_keys", "mbft_cold_keys",
 ]
+# (mbft_key_class_cost, the one declaration that returns uint32_t, is typed in load() but not listed: the
+# header check of tests/test_abi.py reads the int / void / uint64_t / size_t / const char* declarations)
 
 # enum mbft_msg_type / mbft_stage / mbft_validate_flags
 MSG_REQUEST, MSG_REPLY, MSG_PREPARE, MSG_COMMIT, MSG_REQ_VIEW_CHANGE = 1, 2, 3, 4, 5
@@ -108,6 +112,19 @@ ST_REQUEST_SIG, ST_NOT_PRIMARY, ST_PREPARE_UI, ST_COMMIT_FROM_PRIMARY = 1, 2, 3,
 ST_COMMIT_UI, ST_NOT_IMPLEMENTED, ST_STREAM_STOPPED, ST_REPLY_SIG, ST_AFTER_PANIC = 5, 6, 7, 8, 9
 ST_UNKNOWN_TYPE, ST_REPLY_CLIENT_ID = 10, 11
 VF_NO_STREAM_STOP, VF_NO_PANIC_STOP = 1, 2
+
+
+class MbftRebalanceResult(ctypes.Structure):
+    """mbft_rebalance_result"""
+    _fields_ = [
+        ("live_before", ctypes.c_uint64),
+        ("live_after", ctypes.c_uint64),
+        ("pinned_bytes", ctypes.c_uint64),
+        ("over_budget", ctypes.c_uint64),
+        ("promoted", ctypes.c_uint32),
+        ("demoted", ctypes.c_uint32),
+        ("keys_per_rung", ctypes.c_uint32 * 8),
+    ]
 
 
 class MbftMessage(ctypes.Structure):
@@ -262,6 +279,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_remove_public_key": (i, [vp, u32, u32]),
         "mbft_release_slots": (i, [vp, vp, sz]),
         "mbft_key_memory": (i, [vp, vp]),
+        "mbft_age_key_usage": (i, [vp, ctypes.c_uint]),
+        "mbft_set_key_budget": (i, [vp, ctypes.c_uint64]),
+        "mbft_get_key_budget": (i, [vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "mbft_key_class_cost": (u32, [u32]),
+        "mbft_rebalance_keys": (i, [vp, vp, sz, ctypes.c_uint64, ctypes.POINTER(MbftRebalanceResult)]),
+        "mbft_cold_keys": (i, [vp, ctypes.c_uint64, vp, sz, ctypes.POINTER(sz)]),
         "mbft_get_windows": (i, [vp, ctypes.POINTER(i), ctypes.POINTER(i)]),
         "mbft_request_digests_device": (i, [vp, vp, vp, u32, sz, vp, vp]),
         "mbft_sha256_device": (i, [vp, vp, vp, sz, vp, vp]),

@@ -274,6 +274,50 @@ class Authenticator:
         self._check(self.lib.mbft_key_memory(self.ctx, out), "key_memory")
         return int(out[0]), int(out[1]), int(out[2])
 
+    # the key memory budget (include/minbft_gpu.h)
+    def age_key_usage(self, shift: int):
+        """Every use counter shifted right by ``shift`` bits (0..63), so that
+        old use fades."""
+        self._check(self.lib.mbft_age_key_usage(self.ctx, shift), "age_key_usage")
+
+    def set_key_budget(self, nbytes: int):
+        """The bytes of live key data per engine ``rebalance_keys`` plans
+        against; 0 is none."""
+        self._check(self.lib.mbft_set_key_budget(self.ctx, nbytes), "set_key_budget")
+
+    def key_budget(self) -> int:
+        out = ctypes.c_uint64()
+        self._check(self.lib.mbft_get_key_budget(self.ctx, ctypes.byref(out)), "get_key_budget")
+        return out.value
+
+    def key_class_cost(self, cls: int) -> int:
+        """The modelled field reductions of u2 Q in class ``cls`` (a model, not
+        a measurement); 0 for an unknown code."""
+        return int(self.lib.mbft_key_class_cost(cls))
+
+    def rebalance_keys(self, ladder, min_uses: int = 0) -> dict:
+        """Give every key whose class is a rung of ``ladder`` (class codes,
+        cheapest first) the rung of its use count within the budget.  Returns
+        the result as a dict, with ``rc`` the library's status: on a failure
+        part way the dict says what was done and GpuError is raised only when
+        nothing was."""
+        lad = np.ascontiguousarray(ladder, dtype=np.uint32)
+        res = _lib.MbftRebalanceResult()
+        rc = self.lib.mbft_rebalance_keys(self.ctx, lad.ctypes.data, len(lad), min_uses, ctypes.byref(res))
+        if rc < 0 and not (res.promoted or res.demoted):
+            self._check(rc, "rebalance_keys")
+        return {"rc": rc, "live_before": res.live_before, "live_after": res.live_after,
+                "pinned_bytes": res.pinned_bytes, "over_budget": res.over_budget, "promoted": res.promoted,
+                "demoted": res.demoted, "keys_per_rung": list(res.keys_per_rung)[:len(lad)]}
+
+    def cold_keys(self, max_uses: int, cap: int):
+        """(the ``cap`` lowest valid slots whose summed uses are <= max_uses,
+        ascending; how many there are in all)."""
+        out = np.zeros(max(cap, 1), dtype=np.uint32)
+        count = ctypes.c_size_t()
+        self._check(self.lib.mbft_cold_keys(self.ctx, max_uses, out.ctypes.data, cap, ctypes.byref(count)), "cold_keys")
+        return out[:min(cap, count.value)].copy(), count.value
+
     def set_generator_window(self, wbits: int):
         """Rebuild the generator comb table with a window of 4..29 bits."""
         self._check(self.lib.mbft_set_generator_window(self.ctx, wbits), "set_generator_window")

@@ -828,7 +828,8 @@ void mbft_ctx_destroy(mbft_ctx* c) {
                     &c->m_recs, &c->m_bytes, &c->m_chk, &c->m_flag, &c->m_cand, &c->m_chash,
                     &c->m_cslot, &c->m_uniq, &c->m_ref, &c->m_idx, &c->m_callof, &c->m_candof, &c->m_bounds,
                     &c->m_tkeys, &c->m_treps, &c->m_scan, &c->m_fpg, &c->m_info, &c->m_epset,
-                    &c->m_epval, &c->m_cap, &c->m_out, &c->b_bad, &c->m_pack, &c->key_stage})
+                    &c->m_epval, &c->m_cap, &c->m_out, &c->b_bad, &c->m_pack, &c->key_stage,
+                    &c->rank_parts, &c->rank_out, &c->rank_lists})
     b->release();
   for (PinnedBuf* b : {&c->h_e, &c->h_r, &c->h_s, &c->h_slot, &c->h_status, &c->h_udata, &c->h_uoff,
                        &c->h_uidx, &c->h_uep, &c->h_uctr, &c->h_desc, &c->h_small, &c->hm_small,

@@ -448,6 +448,14 @@ struct mbft_ctx {
   size_t acct_slots = 0;
   std::mutex acct_mu;
   std::vector<uint64_t> res_uses, res_rejects;
+  // The key memory budget (mbft_set_key_budget, keys.cpp):
+  // the bytes of live key data per engine mbft_rebalance_keys plans against,
+  // 0 none.  Nothing below is allocated before the first ranking: rank_parts
+  // holds the peers' and the resident verifier's counts beside this engine's
+  // own, rank_out the histogram, the plan and the list counts, rank_lists the
+  // slots that move.
+  uint64_t key_budget = 0;
+  mbft_host::DevBuf rank_parts, rank_out, rank_lists;
 
   // Multi-GPU in one process (mbft_ctx_add_device): peer engines on other
   // devices hold replicas of the comb tables (same slot numbering, same

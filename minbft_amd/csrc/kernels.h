@@ -273,6 +273,49 @@ struct KeyAccount {
   uint64_t* rejects;
 };
 hipError_t key_account(const KeyAccount& a, hipStream_t st);
+// The key memory budget's ranking (key_rank.hip): every slot
+// ranked on the GPU by its use count, one slot per lane, grid-stride on
+// k_key_account's grid.  A slot's count u is the sum of its entry in the
+// `nparts` (0 .. kRankParts) counter arrays of `part` -- one per engine, and
+// the resident verifier's -- each of nslots entries; its bin is
+// key_use_bin(u) (key_plan.h).  A LADDER slot is valid and its class is one of
+// the nladder (1 .. kRankLadder) distinct codes of `ladder`, its rung the
+// code's index.
+constexpr int kRankParts = 4, kRankLadder = 8, kRankBins = 496;
+struct KeyRank {
+  const KeyDesc* keys;
+  uint32_t nslots;
+  int nparts;
+  const uint64_t* part[kRankParts];
+  int nladder;
+  uint32_t ladder[kRankLadder];
+};
+// k_key_age: uses[i] >>= shift, rejects[i] >>= shift for i < n (shift 1 .. 63).
+hipError_t key_age(uint64_t* uses, uint64_t* rejects, size_t n, unsigned shift, hipStream_t st);
+// k_key_add: dst[i] += src[i] for i < n (counter arrays past kRankParts are
+// added into one before the ranking).
+hipError_t key_add(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t st);
+// k_key_hist: out[rung * kRankBins + bin] = the ladder slots of that rung and
+// bin, out[kRankHistOutside] = the valid slots outside the ladder.  out
+// (kRankHistWords words) is zeroed on st first.
+constexpr int kRankHistOutside = kRankLadder * kRankBins, kRankHistWords = kRankHistOutside + 1;
+hipError_t key_hist(const KeyRank& r, uint32_t* out, hipStream_t st);
+// k_key_pick, plan mode: every ladder slot whose target rung,
+// rung_of_bin[its bin] (kRankBins bytes on the device, each < nladder), differs
+// from its rung is appended to list[target], in no order.  count[t] (kRankLadder
+// words, zeroed on st first) receives how many belong on list t; only the first
+// cap[t] of them are written.
+struct KeyPickLists {
+  uint32_t* list[kRankLadder];
+  uint32_t cap[kRankLadder];
+};
+hipError_t key_pick_plan(const KeyRank& r, const uint8_t* rung_of_bin, const KeyPickLists& l, uint32_t* count,
+                         hipStream_t st);
+// k_key_pick, cold mode: the valid slots (of any class) with u <= max_uses,
+// appended to list in no order, the first cap of them; *count (zeroed on st
+// first) receives how many there are in all.
+hipError_t key_pick_cold(const KeyRank& r, uint64_t max_uses, uint32_t* list, uint32_t cap, uint32_t* count,
+                         hipStream_t st);
 // MBFT_SPLIT_MAX (default 256; 0 disables the split form), read once.
 long split_max_env();
 hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const mbft::VerifyPlan& plan, hipStream_t st);

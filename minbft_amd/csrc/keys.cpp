@@ -74,6 +74,18 @@ void count_resident_use(mbft_ctx* c, uint32_t slot, uint8_t status) {
 
 namespace {
 
+// The streams the library launches engine e's batches on, its lanes' among
+// them, have finished (device set): every add of theirs is in the counters.
+int sync_engine_streams(mbft_ctx* c, mbft_ctx* e) {
+  std::vector<mbft_ctx*> own{e};
+  for (mbft_ctx* l : c->lanes)
+    if (l->owner == e) own.push_back(l);
+  for (mbft_ctx* o : own)
+    for (hipStream_t st : {o->stream, o->vstream[0], o->vstream[1]})
+      if (st) HIPCHK(c, hipStreamSynchronize(st));
+  return MBFT_OK;
+}
+
 // Every slot's counts summed over the engines and the resident counter
 // (caller holds KeyWriteGuard: no library batch is in flight; the streams the
 // library launches on are synchronized here).
@@ -85,12 +97,7 @@ int read_usage(mbft_ctx* c, std::vector<uint64_t>& uses, std::vector<uint64_t>& 
   for (mbft_ctx* e : engines_of(c)) {
     if (!e->d_uses || ns == 0) continue;
     if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
-    std::vector<mbft_ctx*> own{e};
-    for (mbft_ctx* l : c->lanes)
-      if (l->owner == e) own.push_back(l);
-    for (mbft_ctx* o : own)
-      for (hipStream_t st : {o->stream, o->vstream[0], o->vstream[1]})
-        if (st) HIPCHK(c, hipStreamSynchronize(st));
+    if (const int rc = sync_engine_streams(c, e)) return rc;
     const size_t m = ns < e->acct_slots ? ns : e->acct_slots;
     HIPCHK(c, hipMemcpyAsync(u.data(), e->d_uses, m * sizeof(uint64_t), hipMemcpyDeviceToHost, e->kstream));
     HIPCHK(c, hipMemcpyAsync(r.data(), e->d_rejects, m * sizeof(uint64_t), hipMemcpyDeviceToHost, e->kstream));
@@ -244,6 +251,86 @@ int release_slots(mbft_ctx* c, const std::vector<uint32_t>& sl) {
   return MBFT_OK;
 }
 
+// ----------------------------------------------------------- the memory budget
+// The key store as the ranking kernels read it (key_rank.hip), on the
+// context's own device: its descriptors, and as `parts` every array of use
+// counts there is -- this engine's own where it stands, the peers' copied
+// into rank_parts (directly, through the host if that fails), the resident
+// verifier's host-side counts uploaded.  Parts past kRankParts are added into
+// the last one.  Every library stream is synchronized first, as read_usage
+// does.  Returns with kstream idle.
+int rank_store(mbft_ctx* c, const uint32_t* ladder, size_t nladder, mbft_launch::KeyRank& R) {
+  using mbft_launch::kRankParts;
+  if (hipSetDevice(c->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+  if (const int rc = upload_keydesc(c)) return rc;
+  const size_t ns = c->keydesc.size();
+  R = mbft_launch::KeyRank{};
+  R.keys = c->d_keys.as<mbft::KeyDesc>();
+  R.nslots = (uint32_t)ns;
+  R.nladder = (int)nladder;
+  for (size_t j = 0; j < nladder; j++) R.ladder[j] = ladder[j];
+  if (ns == 0) return MBFT_OK;
+  std::vector<uint64_t> res;
+  {
+    std::lock_guard<std::mutex> g(c->acct_mu);
+    res.assign(c->res_uses.begin(), c->res_uses.begin() + std::min(ns, c->res_uses.size()));
+  }
+  const std::vector<mbft_ctx*> engines = engines_of(c);
+  size_t nscratch = res.empty() ? 0 : 1;
+  for (mbft_ctx* e : engines)
+    if (e->d_uses && (e != c || e->acct_slots < ns)) nscratch++;
+  uint64_t* scratch = nullptr;
+  if (nscratch) {
+    HIPCHK(c, c->rank_parts.ensure(nscratch * ns * sizeof(uint64_t)));
+    scratch = c->rank_parts.as<uint64_t>();
+    HIPCHK(c, hipMemsetAsync(scratch, 0, nscratch * ns * sizeof(uint64_t), c->kstream));
+    HIPCHK(c, hipStreamSynchronize(c->kstream));
+  }
+  std::vector<const uint64_t*> src;
+  std::vector<uint64_t> via;
+  size_t used = 0;  // parts of scratch taken
+  for (mbft_ctx* e : engines) {
+    if (!e->d_uses) continue;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    if (const int rc = sync_engine_streams(c, e)) return rc;
+    if (e == c && e->acct_slots >= ns) {
+      src.push_back(e->d_uses);
+      continue;
+    }
+    uint64_t* dst = scratch + used++ * ns;
+    const size_t bytes = std::min(ns, e->acct_slots) * sizeof(uint64_t);
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    hipError_t err = e->device == c->device
+                         ? hipMemcpyAsync(dst, e->d_uses, bytes, hipMemcpyDeviceToDevice, c->kstream)
+                         : hipMemcpyPeerAsync(dst, c->device, e->d_uses, e->device, bytes, c->kstream);
+    if (err == hipSuccess) err = hipStreamSynchronize(c->kstream);
+    if (err != hipSuccess) {  // no direct path between the two devices: through the host
+      (void)hipGetLastError();
+      via.resize(bytes / sizeof(uint64_t));
+      if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+      HIPCHK(c, hipMemcpyAsync(via.data(), e->d_uses, bytes, hipMemcpyDeviceToHost, e->kstream));
+      HIPCHK(c, hipStreamSynchronize(e->kstream));
+      if (hipSetDevice(c->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+      HIPCHK(c, hipMemcpyAsync(dst, via.data(), bytes, hipMemcpyHostToDevice, c->kstream));
+      HIPCHK(c, hipStreamSynchronize(c->kstream));
+    }
+    src.push_back(dst);
+  }
+  if (hipSetDevice(c->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+  if (!res.empty()) {
+    uint64_t* dst = scratch + used * ns;
+    HIPCHK(c, hipMemcpyAsync(dst, res.data(), res.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->kstream));
+    HIPCHK(c, hipStreamSynchronize(c->kstream));
+    src.push_back(dst);
+  }
+  // (src[0] is this engine's own array or scratch, every later one scratch: the sum goes into scratch)
+  for (size_t k = kRankParts; k < src.size(); k++)
+    HIPCHK(c, mbft_launch::key_add(const_cast<uint64_t*>(src[kRankParts - 1]), src[k], ns, c->kstream));
+  HIPCHK(c, hipStreamSynchronize(c->kstream));
+  R.nparts = (int)std::min(src.size(), (size_t)kRankParts);
+  for (int p = 0; p < R.nparts; p++) R.part[p] = src[(size_t)p];
+  return MBFT_OK;
+}
 
 }  // namespace
 
@@ -390,6 +477,156 @@ int mbft_key_memory(const mbft_ctx* c, uint64_t out[3]) {
   uint64_t blocks = 0;
   for (size_t b : c->tab_sizes) blocks += b;
   out[2] = blocks;
+  return MBFT_OK;
+}
+
+int mbft_age_key_usage(mbft_ctx* c, unsigned shift) {
+  if (!c || c->owner || shift >= 64) return MBFT_ERR_ARG;
+  if (shift == 0) return MBFT_OK;
+  KeyWriteGuard g(c);
+  for (mbft_ctx* e : engines_of(c)) {
+    if (!e->d_uses) continue;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    if (const int rc = sync_engine_streams(c, e)) return rc;  // adds still in flight belong to the old count
+    HIPCHK(c, mbft_launch::key_age(e->d_uses, e->d_rejects, e->acct_slots, shift, e->kstream));
+    HIPCHK(c, hipStreamSynchronize(e->kstream));
+  }
+  (void)hipSetDevice(c->device);
+  std::lock_guard<std::mutex> am(c->acct_mu);
+  for (uint64_t& v : c->res_uses) v >>= shift;
+  for (uint64_t& v : c->res_rejects) v >>= shift;
+  return MBFT_OK;
+}
+
+int mbft_set_key_budget(mbft_ctx* c, uint64_t bytes) {
+  if (!c || c->owner) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  c->key_budget = bytes;
+  return MBFT_OK;
+}
+
+int mbft_get_key_budget(const mbft_ctx* c, uint64_t* bytes) {
+  if (!c || !bytes) return MBFT_ERR_ARG;
+  *bytes = c->key_budget;
+  return MBFT_OK;
+}
+
+uint32_t mbft_key_class_cost(uint32_t cls) { return mbft::key_class_cost(cls); }
+
+int mbft_rebalance_keys(mbft_ctx* c, const uint32_t* ladder, size_t nladder, uint64_t min_uses,
+                        mbft_rebalance_result* out) {
+  using namespace mbft_launch;
+  if (out) *out = mbft_rebalance_result{};
+  if (!c || c->owner || !out || !mbft::rebalance_ladder_ok(ladder, nladder)) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  // (counts that are all zero would demote every key)
+  if (!c->accounting.load()) return fail(c, MBFT_ERR_STATE, "mbft_rebalance_keys: key accounting is off");
+  if (c->key_budget == 0) return fail(c, MBFT_ERR_STATE, "mbft_rebalance_keys: no key budget is set");
+  const int L = (int)nladder;
+  KeyRank R;
+  if (const int rc = rank_store(c, ladder, nladder, R)) return rc;
+  out->live_before = out->live_after = c->live_bytes;
+  // the histogram: a few kilobytes, whatever the slots
+  HIPCHK(c, c->rank_out.ensure(sizeof(uint32_t) * (kRankHistWords + kRankLadder) + kRankBins));
+  uint32_t* d_hist = c->rank_out.as<uint32_t>();
+  uint32_t* d_count = d_hist + kRankHistWords;
+  uint8_t* d_rob = reinterpret_cast<uint8_t*>(d_count + kRankLadder);
+  std::vector<uint32_t> hist(kRankHistWords);
+  HIPCHK(c, key_hist(R, d_hist, c->kstream));
+  HIPCHK(c, hipMemcpyAsync(hist.data(), d_hist, sizeof(uint32_t) * kRankHistWords, hipMemcpyDeviceToHost, c->kstream));
+  HIPCHK(c, hipStreamSynchronize(c->kstream));
+  uint64_t of_bin[kRankBins] = {}, ladder_bytes = 0;
+  for (int j = 0; j < L; j++)
+    for (int b = 0; b < kRankBins; b++) {
+      const uint32_t k = hist[(size_t)j * kRankBins + b];
+      of_bin[b] += k;
+      out->keys_per_rung[j] += k;
+      ladder_bytes += k * mbft::key_class_bytes(ladder[j]);
+    }
+  // valid keys outside the ladder are pinned: they keep their class and their bytes count
+  out->pinned_bytes = c->live_bytes - ladder_bytes;
+  const uint64_t avail = c->key_budget > out->pinned_bytes ? c->key_budget - out->pinned_bytes : 0;
+  const mbft::RebalancePlan plan = mbft::rebalance_plan(of_bin, ladder, nladder, avail, min_uses);
+  if (plan.excess) out->over_budget = out->pinned_bytes + plan.bytes - c->key_budget;
+  // every list's length is known from the histogram: the slots of another rung in the bins that go to t
+  KeyPickLists lists{};
+  size_t moving = 0;
+  for (int b = 0; b < kRankBins; b++)
+    for (int j = 0; j < L; j++)
+      if (j != plan.rung_of_bin[b]) lists.cap[plan.rung_of_bin[b]] += hist[(size_t)j * kRankBins + b];
+  for (int t = 0; t < L; t++) moving += lists.cap[t];
+  if (moving == 0) return MBFT_OK;
+  HIPCHK(c, c->rank_lists.ensure(moving * sizeof(uint32_t)));
+  for (size_t t = 0, off = 0; t < nladder; off += lists.cap[t++]) lists.list[t] = c->rank_lists.as<uint32_t>() + off;
+  HIPCHK(c, hipMemcpyAsync(d_rob, plan.rung_of_bin, kRankBins, hipMemcpyHostToDevice, c->kstream));
+  HIPCHK(c, key_pick_plan(R, d_rob, lists, d_count, c->kstream));
+  uint32_t count[kRankLadder];
+  std::vector<uint32_t> moved(moving);
+  HIPCHK(c, hipMemcpyAsync(count, d_count, sizeof(count), hipMemcpyDeviceToHost, c->kstream));
+  HIPCHK(c, hipMemcpyAsync(moved.data(), c->rank_lists.p, moving * sizeof(uint32_t), hipMemcpyDeviceToHost, c->kstream));
+  HIPCHK(c, hipStreamSynchronize(c->kstream));
+  for (int t = 0; t < L; t++)
+    if (count[t] != lists.cap[t]) return fail(c, MBFT_ERR_STATE, "mbft_rebalance_keys: the lists disagree with the histogram");
+  // per target rung the keys that come down to it and those that go up to it, each ascending
+  std::vector<uint32_t> down[kRankLadder], up[kRankLadder];
+  for (size_t t = 0, off = 0; t < nladder; off += lists.cap[t++])
+    for (size_t k = off; k < off + lists.cap[t]; k++) {
+      const uint32_t s = moved[k];
+      if (s >= c->keydesc.size() || !c->keydesc[s].valid ||
+          std::find(ladder, ladder + nladder, c->keydesc[s].wbits) == ladder + nladder)
+        return fail(c, MBFT_ERR_STATE, "mbft_rebalance_keys: a listed slot is not a ladder key");
+      (mbft::key_class_bytes(c->keydesc[s].wbits) > mbft::key_class_bytes(ladder[t]) ? down[t] : up[t]).push_back(s);
+    }
+  // demotions first, rung 0 upwards, then promotions from the top rung downwards: the promotions take the
+  // pieces the demotions released.  A failure stops the walk; every bulk step is all or nothing.
+  int rc = MBFT_OK;
+  auto step = [&](std::vector<uint32_t>& sl, int t, uint32_t* tally) {
+    if (rc != MBFT_OK || sl.empty()) return;
+    std::sort(sl.begin(), sl.end());
+    std::vector<int> from(sl.size());
+    for (size_t k = 0; k < sl.size(); k++)
+      from[k] = (int)(std::find(ladder, ladder + nladder, c->keydesc[sl[k]].wbits) - ladder);
+    rc = reclass(c, sl, ladder[t]);
+    if (rc != MBFT_OK) return;
+    for (int j : from) out->keys_per_rung[j]--;
+    out->keys_per_rung[t] += (uint32_t)sl.size();
+    *tally += (uint32_t)sl.size();
+  };
+  for (int t = 0; t < L; t++) step(down[t], t, &out->demoted);
+  for (int t = L - 1; t >= 0; t--) step(up[t], t, &out->promoted);
+  out->live_after = c->live_bytes;
+  return rc;
+}
+
+int mbft_cold_keys(mbft_ctx* c, uint64_t max_uses, uint32_t* slots_out, size_t cap, size_t* count) {
+  using namespace mbft_launch;
+  if (count) *count = 0;
+  if (!c || c->owner || !count || (cap && !slots_out)) return MBFT_ERR_ARG;
+  KeyWriteGuard g(c);
+  KeyRank R;
+  if (const int rc = rank_store(c, nullptr, 0, R)) return rc;
+  if (R.nslots == 0) return MBFT_OK;
+  HIPCHK(c, c->rank_out.ensure(sizeof(uint32_t) * (kRankHistWords + kRankLadder) + kRankBins));
+  uint32_t* d_count = c->rank_out.as<uint32_t>();
+  // room for `cap` first; if more are cold, once more with room for all, so that the cap LOWEST are returned
+  uint32_t room = (uint32_t)std::min<size_t>(cap, R.nslots), total = 0;
+  std::vector<uint32_t> cold;
+  for (int pass = 0; pass < 2; pass++) {
+    HIPCHK(c, c->rank_lists.ensure((room ? room : 1) * sizeof(uint32_t)));
+    HIPCHK(c, key_pick_cold(R, max_uses, c->rank_lists.as<uint32_t>(), room, d_count, c->kstream));
+    HIPCHK(c, hipMemcpyAsync(&total, d_count, sizeof(total), hipMemcpyDeviceToHost, c->kstream));
+    HIPCHK(c, hipStreamSynchronize(c->kstream));
+    if (total <= room || cap == 0) break;
+    room = total;
+  }
+  *count = total;
+  cold.resize(std::min(room, total));
+  if (!cold.empty()) {
+    HIPCHK(c, hipMemcpyAsync(cold.data(), c->rank_lists.p, cold.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->kstream));
+    HIPCHK(c, hipStreamSynchronize(c->kstream));
+  }
+  std::sort(cold.begin(), cold.end());
+  for (size_t k = 0; k < cold.size() && k < cap; k++) slots_out[k] = cold[k];
   return MBFT_OK;
 }
 
