@@ -394,6 +394,41 @@ uint32_t mbft_key_class_cost(uint32_t cls);
 int mbft_rebalance_keys(mbft_ctx* ctx, const uint32_t* ladder, size_t nladder, uint64_t min_uses,
                         mbft_rebalance_result* out);
 int mbft_cold_keys(mbft_ctx* ctx, uint64_t max_uses, uint32_t* slots_out, size_t cap, size_t* count);
+/* The verified-call memo: accepted signature checks
+ * remembered across batches.  MinBFT validates nested messages -- a COMMIT
+ * re-validates its embedded PREPARE (core/commit.go:82), the PREPARE its
+ * embedded REQUEST (core/prepare.go:55) -- so a backup makes 3n - 3
+ * authenticator calls a request of which n are distinct (SURVEY section 8(f)
+ * row 2, Appendix B), and the copies arrive in different batches.  The result
+ * of a signature check is a pure function of (key, e, r, s): with the memo on,
+ * the message layer's device passes (mbft_check_messages* / mbft_validate_
+ * messages* past the small route) look every unique call up in a table of
+ * accepted (key slot, e, r, s) tuples in device memory; a hit is accepted
+ * without running the check, only the misses go to the verifier, and the
+ * accepted misses are then remembered.  Only accepts are remembered.  Every hit
+ * is confirmed by comparing the whole tuple.
+ *   What the memo does NOT change: any status or reject kind, the USIG epoch
+ *   step (applied per check afterwards, as before: e holds the epoch and the
+ *   counter, the step is not part of the tuple), where a stream stops, the
+ *   per-key use counts.  Off (the default), no kernel of it is launched.
+ *   mbft_set_verified_memo: `bytes` of device memory on every engine for the
+ *     table, rounded down to two generations of a power-of-two number of
+ *     128-byte entries (at least 2 x 1,024: MBFT_ERR_ARG below); 0 turns the
+ *     memo off and frees it.  Setting it again starts empty.  MBFT_ERR_NOMEM
+ *     leaves the previous state in place.
+ *   mbft_get_verified_memo: the rounded size in use (0: off).
+ *   mbft_verified_memo_stats: lookups, hits, inserts, dropped (inserts that
+ *     found their probe window full), rotations, clears, summed over the
+ *     engines; lookups - hits is what went to the verifier.
+ *   mbft_clear_verified_memo: forget everything.  The library does so itself
+ *     whenever a slot number can come to mean another point
+ *     (mbft_remove_public_key, mbft_release_slots, mbft_clear_keys);
+ *     re-classing, promotion and mbft_rebalance_keys keep the point and the
+ *     memo. */
+int mbft_set_verified_memo(mbft_ctx* ctx, uint64_t bytes);
+int mbft_get_verified_memo(mbft_ctx* ctx, uint64_t* bytes);
+int mbft_verified_memo_stats(mbft_ctx* ctx, uint64_t out[6]);
+int mbft_clear_verified_memo(mbft_ctx* ctx);
 /* USIG scheme present (authenticator.go:102-110: absent without a USIG). */
 int mbft_enable_usig(mbft_ctx* ctx, int enabled);
 /* Private key for GenerateMessageAuthenTag in an ECDSA role. */

@@ -102,6 +102,7 @@ EXPORTED = [
     "mbft_remove_public_key", "mbft_release_slots", "mbft_key_memory",
     "mbft_age_key_usage", "mbft_set_key_budget", "mbft_get_key_budget",
     "mbft_rebalance_keys", "mbft_cold_keys",
+    "mbft_set_verified_memo", "mbft_get_verified_memo", "mbft_verified_memo_stats", "mbft_clear_verified_memo",
 ]
 # (mbft_key_class_cost, the one declaration that returns uint32_t, is typed in load() but not listed: the
 # header check of tests/test_abi.py reads the int / void / uint64_t / size_t / const char* declarations)
@@ -285,6 +286,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_key_class_cost": (u32, [u32]),
         "mbft_rebalance_keys": (i, [vp, vp, sz, ctypes.c_uint64, ctypes.POINTER(MbftRebalanceResult)]),
         "mbft_cold_keys": (i, [vp, ctypes.c_uint64, vp, sz, ctypes.POINTER(sz)]),
+        "mbft_set_verified_memo": (i, [vp, ctypes.c_uint64]),
+        "mbft_get_verified_memo": (i, [vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "mbft_verified_memo_stats": (i, [vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "mbft_clear_verified_memo": (i, [vp]),
         "mbft_get_windows": (i, [vp, ctypes.POINTER(i), ctypes.POINTER(i)]),
         "mbft_request_digests_device": (i, [vp, vp, vp, u32, sz, vp, vp]),
         "mbft_sha256_device": (i, [vp, vp, vp, sz, vp, vp]),

@@ -318,6 +318,29 @@ class Authenticator:
         self._check(self.lib.mbft_cold_keys(self.ctx, max_uses, out.ctypes.data, cap, ctypes.byref(count)), "cold_keys")
         return out[:min(cap, count.value)].copy(), count.value
 
+    # the verified-call memo (include/minbft_gpu.h)
+    def set_verified_memo(self, nbytes: int):
+        """Remember accepted signature checks across batches in ``nbytes`` of
+        device memory per engine (rounded down to two generations of a power of
+        two of 128-byte entries, at least 2 x 1,024); 0 turns the memo off."""
+        self._check(self.lib.mbft_set_verified_memo(self.ctx, nbytes), "set_verified_memo")
+
+    def verified_memo(self) -> int:
+        """The memo's rounded size in use, 0 when off."""
+        out = ctypes.c_uint64()
+        self._check(self.lib.mbft_get_verified_memo(self.ctx, ctypes.byref(out)), "get_verified_memo")
+        return out.value
+
+    def verified_memo_stats(self) -> dict:
+        """lookups, hits, inserts, dropped, rotations, clears, summed over the
+        engines; lookups - hits is what went to the verifier."""
+        out = (ctypes.c_uint64 * 6)()
+        self._check(self.lib.mbft_verified_memo_stats(self.ctx, out), "verified_memo_stats")
+        return dict(zip(("lookups", "hits", "inserts", "dropped", "rotations", "clears"), (int(v) for v in out)))
+
+    def clear_verified_memo(self):
+        self._check(self.lib.mbft_clear_verified_memo(self.ctx), "clear_verified_memo")
+
     def set_generator_window(self, wbits: int):
         """Rebuild the generator comb table with a window of 4..29 bits."""
         self._check(self.lib.mbft_set_generator_window(self.ctx, wbits), "set_generator_window")

@@ -493,10 +493,20 @@ int register_points_engine(mbft_ctx* c, const uint8_t* xy64, size_t n, uint32_t*
   return MBFT_OK;
 }
 
+// Small batches: no batched s^-1 chain (five dependent launches, ~180 us
+// of latency); the small-batch forms invert s themselves (verify_plan.h).
+// Env MBFT_LANE_INV_MAX (default 4096 items; 0 disables).
+static size_t lane_inv_max_env() {
+  static const size_t v = mbft::env_size("MBFT_LANE_INV_MAX", 4096);
+  return v;
+}
+
 // Verify n decoded items (device pointers) -> device status, on stream st.
-int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uint8_t* d_s,
-                  const uint32_t* d_slot, size_t n, uint8_t* d_status, hipStream_t st,
-                  bool host_status, bool latency, const uint32_t* d_winv, const uint32_t* d_count) {
+// memo_misses: the items are the misses of a memo pass (verify_device below):
+// the plan does not account, the pass does over its original items.
+static int verify_device_run(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uint8_t* d_s,
+                             const uint32_t* d_slot, size_t n, uint8_t* d_status, hipStream_t st, bool host_status,
+                             bool latency, const uint32_t* d_winv, const uint32_t* d_count, bool memo_misses) {
   if (n == 0) return MBFT_OK;
   const mbft_ctx* tb = tabs(c);  // the tables (a lane reads its owner's)
   const int k = c->pipe;
@@ -504,18 +514,17 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
   const size_t wwords = mbft_launch::ninv_workspace_words((long)n);
   HIPCHK(c, c->ws[k].ensure(wwords * 4));
   HIPCHK(c, c->winv[k].ensure((size_t)9 * n * 4));
-  // Small batches: no batched s^-1 chain (five dependent launches, ~180 us
-  // of latency); the small-batch forms invert s themselves (verify_plan.h).
-  // Env MBFT_LANE_INV_MAX (default 4096 items; 0 disables).
-  static const size_t lane_inv_max = mbft::env_size("MBFT_LANE_INV_MAX", 4096);
+  const size_t lane_inv_max = lane_inv_max_env();
   // The batch's form, decided once: it sizes slowq[k] (the spill planes of
   // the grid that runs), names the s^-1 to run here and goes to the launcher.
   const mbft::InvSource src = mbft::verify_inv_source((long)n, lane_inv_max, d_winv != nullptr, d_count != nullptr);
-  const mbft::VerifyPlan plan = mbft::verify_plan_account(
-      mbft::verify_plan((long)n, src, d_count != nullptr, /*has_planes_ws=*/!d_winv,
-                        tb->split_max < 0 ? mbft_launch::split_max_env() : tb->split_max,
-                        tb->small_inv < 0 ? 2 : tb->small_inv),
-      tb->accounting.load(std::memory_order_relaxed) && tb->d_uses != nullptr);
+  const mbft::VerifyPlan plan = mbft::verify_plan_memo(
+      mbft::verify_plan_account(
+          mbft::verify_plan((long)n, src, d_count != nullptr, /*has_planes_ws=*/!d_winv,
+                            tb->split_max < 0 ? mbft_launch::split_max_env() : tb->split_max,
+                            tb->small_inv < 0 ? 2 : tb->small_inv),
+          tb->accounting.load(std::memory_order_relaxed) && tb->d_uses != nullptr),
+      memo_misses);
   HIPCHK(c, c->slowq[k].ensure(mbft::verify_slowq_words((long)n, plan) * 4));
   mbft_ctx::Ev ev{};
   if (c->prof) {
@@ -613,6 +622,69 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
   // have run on another stream)
   HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));
   return verify_and_mark_done(winv);
+}
+
+// The same under the owner's verified-call memo (memo_plan.h, memo.hip;
+// DESIGN.md §4.12) where `memo` asks for it and the memo can serve the pass: one
+// exists, no clear is pending, and the host brought no s^-1 planes (those are
+// indexed by item).  k_memo_probe accepts the remembered calls and compacts
+// the rest into memo_scr[k]; the verifier runs over the compacted items only;
+// k_memo_commit scatters their statuses back and remembers the accepted ones;
+// the use-count stage, where on, runs last over the ORIGINAL items, so the
+// counts are the same with the memo on or off.  Where the plan takes a
+// small-batch form anyway (n <= MBFT_LANE_INV_MAX, or the caller's count is on
+// the device) the miss count stays on the device as the verifier's count.
+// Otherwise the host reads it (4 bytes, one synchronize of st) and plans on
+// it: no miss, no verify launch.  The caller ends the pass (MemoPassGuard).
+int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uint8_t* d_s,
+                  const uint32_t* d_slot, size_t n, uint8_t* d_status, hipStream_t st,
+                  bool host_status, bool latency, const uint32_t* d_winv, const uint32_t* d_count, bool memo) {
+  if (n == 0) return MBFT_OK;
+  MemoView mv{};
+  if (!memo || d_winv != nullptr || !memo_pass_begin(c, st, n, &mv))
+    return verify_device_run(c, d_e, d_r, d_s, d_slot, n, d_status, st, host_status, latency, d_winv, d_count, false);
+  const mbft_ctx* tb = tabs(c);
+  const int k = c->pipe;  // the buffers the misses' verify takes next
+  const mbft::MemoScratch L = mbft::memo_scratch(n);
+  HIPCHK(c, c->memo_scr[k].ensure(L.bytes));
+  uint8_t* const scr = c->memo_scr[k].as<uint8_t>();
+  uint32_t* const miss = reinterpret_cast<uint32_t*>(scr + L.count);
+  uint32_t* const slot_c = reinterpret_cast<uint32_t*>(scr + L.slot);
+  uint32_t* const origin = reinterpret_cast<uint32_t*>(scr + L.origin);
+  const mbft::KeyDesc* keys = tb->d_keys.as<mbft::KeyDesc>();
+  const uint32_t nslots = (uint32_t)tb->slots.size();
+  HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // memo_scr[k] reuse
+  HIPCHK(c, hipMemsetAsync(miss, 0, 64, st));
+  const mbft_launch::MemoProbe mp{d_e, d_r, d_s, d_slot, (long)n, d_count, keys, nslots, mv.young, mv.old, mv.entries,
+                                  d_status, scr + L.e, scr + L.r, scr + L.s, slot_c, origin, miss, mv.stats, nullptr};
+  HIPCHK(c, mbft_launch::memo_probe(mp, st));
+  size_t m = n;  // the verifier's item count: an upper bound while the count stays on the device
+  const uint32_t* cnt = miss;
+  if (n > lane_inv_max_env() && d_count == nullptr) {
+    HIPCHK(c, c->memo_cnt.ensure(64));
+    HIPCHK(c, hipMemcpyAsync(c->memo_cnt.p, miss, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    m = *c->memo_cnt.as<uint32_t>();
+    if (m > n) return fail(c, MBFT_ERR_STATE, "verified-call memo: miss count past the batch");
+    cnt = nullptr;
+  }
+  if (m != 0) {
+    const int rc = verify_device_run(c, scr + L.e, scr + L.r, scr + L.s, slot_c, m, scr + L.status, st, host_status,
+                                     latency, nullptr, cnt, true);
+    if (rc) return rc;
+    // (n, not m: the commit stops at the miss count itself, and origin indexes the ORIGINAL items)
+    const mbft_launch::MemoCommit mc{scr + L.e, scr + L.r, scr + L.s, slot_c, origin, scr + L.status, (long)n, miss,
+                                     keys, nslots, mv.young, mv.entries, d_status, mv.stats, nullptr};
+    HIPCHK(c, mbft_launch::memo_commit(mc, st));
+  } else {
+    c->pipe = (k + 1) % mbft_ctx::kPipe;
+  }
+  if (tb->accounting.load(std::memory_order_relaxed) && tb->d_uses != nullptr) {
+    const mbft_launch::KeyAccount ka{d_slot, d_status, (long)n, d_count, keys, nslots, tb->d_uses, tb->d_rejects};
+    HIPCHK(c, mbft_launch::key_account(ka, st));
+  }
+  HIPCHK(c, hipEventRecord(c->ev_done[k], st));  // (again: memo_scr[k] is read until here)
+  return MBFT_OK;
 }
 
 // Host buffers in, host status out, on ONE engine.
@@ -853,6 +925,9 @@ void mbft_ctx_destroy(mbft_ctx* c) {
   c->d_keys.release();
   if (c->d_uses) hipFree(c->d_uses);
   if (c->d_rejects) hipFree(c->d_rejects);
+  memo_free(c);
+  for (int k = 0; k < mbft_ctx::kPipe; k++) c->memo_scr[k].release();
+  c->memo_cnt.release();
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1007,6 +1082,9 @@ int mbft_ctx_add_device(mbft_ctx* c, int device) {
     p->accounting.store(true);
     if (const int grc = grow_key_counters(p)) return bail(grc, "peer engine: " + p->err);
   }
+  if (c->memo) {  // the verified-call memo is on every table engine
+    if (const int mrc = memo_alloc_engine(c, p, c->memo->rot.entries)) return bail(mrc, "peer engine: verified-call memo");
+  }
   p->prof = false;
   p->split_max = c->split_max;
   p->small_inv = c->small_inv;
@@ -1155,6 +1233,8 @@ int mbft_clear_keys(mbft_ctx* c) {
   c->slot_refs.clear();
   c->slot_raw.clear();
   c->live_bytes = 0;
+  // every slot number is free to mean another point: the verified-call memo goes
+  if (const int rc = memo_clear_engine(c, c)) return rc;
   if (c->d_uses) {
     HIPCHK(c, hipMemset(c->d_uses, 0, c->acct_slots * sizeof(uint64_t)));
     HIPCHK(c, hipMemset(c->d_rejects, 0, c->acct_slots * sizeof(uint64_t)));

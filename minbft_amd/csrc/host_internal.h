@@ -24,6 +24,7 @@
 #include "env.h"
 #include "kernels.h"
 #include "key_plan.h"
+#include "memo_plan.h"
 #include "sign_kernels.h"
 #include "sha256.h"
 
@@ -350,6 +351,34 @@ struct UsigCall {
 
 struct Resident;  // the resident single-call verifier (resident.cpp)
 
+// The verified-call memo of ONE table engine (mbft_set_verified_memo, keys.cpp;
+// memo_plan.h): accepted (slot, e, r, s) tuples in device
+// memory that outlive a batch, shared by the engine and its lanes.  Everything
+// but the device pointers is under `m`.  A generation is cleared only while no
+// memo pass of the engine is in flight: `inflight` counts them, rotate_wanted /
+// clear_wanted ask for a clear; while either is set new passes run without the
+// memo, and the pass that brings inflight to zero clears (a memset on its own
+// stream, ev_clear behind it: a later pass on another stream waits for that
+// event, no host thread does), swaps and lifts the flags.
+struct VerifiedMemo {
+  std::mutex m;
+  uint32_t* tab = nullptr;      // two generations of rot.entries entries, generation 1 after 0
+  uint64_t* d_stats = nullptr;  // mbft_launch::kMemoStats counters
+  mbft::MemoRotation rot;
+  int inflight = 0;
+  bool rotate_wanted = false, clear_wanted = false;
+  hipEvent_t ev_clear = nullptr;
+  bool ev_pending = false;  // ev_clear may not have completed yet
+  uint64_t clears = 0;
+};
+// A memo pass of an engine that has begun and not yet ended: its memo, the
+// stream its kernels run on, the unique calls it counts for the rotation rule.
+struct MemoOpen {
+  VerifiedMemo* memo;
+  hipStream_t st;
+  uint64_t calls;
+};
+
 }  // namespace mbft_host
 
 struct mbft_ctx {
@@ -456,6 +485,16 @@ struct mbft_ctx {
   // slots that move.
   uint64_t key_budget = 0;
   mbft_host::DevBuf rank_parts, rank_out, rank_lists;
+  // The verified-call memo: `memo` on a table engine (null: off), owned like
+  // d_uses and read by the engine's lanes through tabs().  Per engine and lane:
+  // one pass's scratch beside slowq[k] (memo_scratch), the page-locked word the
+  // read-back route's miss count lands in, and the passes begun and not ended.
+  // memo_guards: the MemoPassGuards in scope on this engine; verify_device runs
+  // a pass under the memo only while there is one, so no pass can stay open.
+  mbft_host::VerifiedMemo* memo = nullptr;
+  mbft_host::PinnedBuf memo_cnt;
+  std::vector<mbft_host::MemoOpen> memo_open;
+  int memo_guards = 0;
 
   // Multi-GPU in one process (mbft_ctx_add_device): peer engines on other
   // devices hold replicas of the comb tables (same slot numbering, same
@@ -509,6 +548,7 @@ struct mbft_ctx {
   mbft_host::DevBuf winv[kPipe], ws[kPipe], slowq[kPipe];
   hipEvent_t ev_in = nullptr, ev_inv[kPipe] = {}, ev_done[kPipe] = {};
   int pipe = 0;
+  mbft_host::DevBuf memo_scr[kPipe];  // the verified-call memo's scratch of one pass, beside slowq[k]
 
   // Batch pipeline (batch.cpp): host workers fill page-locked staging chunk
   // by chunk; each chunk's H2D runs on `cstream` while the workers fill the
@@ -773,7 +813,41 @@ void count_resident_use(mbft_ctx* c, uint32_t slot, uint8_t status);
 int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uint8_t* d_s,
                   const uint32_t* d_slot, size_t n, uint8_t* d_status, hipStream_t st,
                   bool host_status = false, bool latency = false,
-                  const uint32_t* d_winv = nullptr, const uint32_t* d_count = nullptr);
+                  const uint32_t* d_winv = nullptr, const uint32_t* d_count = nullptr, bool memo = false);
+// The verified-call memo (keys.cpp).  memo_pass_begin: true where engine g's
+// pass of `calls` unique calls on stream st runs under its owner's memo -- one
+// exists, no clear is pending -- with the pass counted in flight and *v the
+// table as the pass sees it.  Every such pass ends in memo_pass_end(g): the
+// streams of g's open passes are synchronized, their calls go to the rotation
+// rule, and the pass that leaves the memo quiet performs a wanted clear.
+// MemoPassGuard does that at the end of the scope that launches the pass;
+// without one in scope memo_pass_begin refuses, so a caller that forgets it
+// runs plain verifies instead of leaving a pass in flight for ever.
+// memo_clear_engine: both generations of table engine e go (a slot number may
+// come to mean another point), now if no pass is in flight, else by the last
+// one.  memo_free: at destroy.
+struct MemoView {
+  uint32_t* young;
+  uint32_t* old;
+  uint64_t entries;
+  uint64_t* stats;
+};
+bool memo_pass_begin(mbft_ctx* g, hipStream_t st, uint64_t calls, MemoView* v);
+void memo_pass_end(mbft_ctx* g);
+struct MemoPassGuard {
+  mbft_ctx* g;
+  explicit MemoPassGuard(mbft_ctx* e) : g(e) { g->memo_guards++; }
+  ~MemoPassGuard() {
+    if (--g->memo_guards == 0 && !g->memo_open.empty()) memo_pass_end(g);
+  }
+  MemoPassGuard(const MemoPassGuard&) = delete;
+  MemoPassGuard& operator=(const MemoPassGuard&) = delete;
+};
+int memo_clear_engine(mbft_ctx* c, mbft_ctx* e);
+// memo_alloc_engine: an empty memo of two generations of `entries` on table
+// engine e (an engine added while the context has one).
+int memo_alloc_engine(mbft_ctx* c, mbft_ctx* e, uint64_t entries);
+void memo_free(mbft_ctx* e);
 // s^-1 R mod N of n big-endian s values into 9 planes of n 29-bit limbs (the
 // k_verify_split form); zeros where s is 0 or >= N (the kernel rejects those
 // before reading w).  Lone calls (batch.cpp).

@@ -273,6 +273,64 @@ struct KeyAccount {
   uint64_t* rejects;
 };
 hipError_t key_account(const KeyAccount& a, hipStream_t st);
+// The verified-call memo's two stages (memo.hip, memo_plan.h; DESIGN.md
+// §4.12) around the verify of a pass.  The table: two generations of `entries`
+// (a power of two) 128-byte entries each, `young` and `old`.  stats: four
+// 64-bit counters on the device -- lookups, hits, inserts, dropped -- added to
+// with one relaxed agent-scope atomic a wave.  e, r, s and their compacted
+// copies are 16-byte aligned.
+constexpr int kMemoStatLookups = 0, kMemoStatHits = 1, kMemoStatInserts = 2, kMemoStatDropped = 3, kMemoStats = 4;
+// k_memo_probe, one item per lane: an item under a real valid key (slot <
+// nslots and KeyDesc.valid) is looked up in the young generation, then the old
+// one; a hit writes MBFT_ACCEPT to status[i].  Every other item -- misses, slot
+// words >= nslots (the host-decided kHostSlot | status words among them),
+// invalid slots -- is appended, in no order, to e_c / r_c / s_c / slot_c with
+// its index in origin; *miss (zeroed on st first by the caller) receives how
+// many.  ndev (optional): the item count on the device; nothing at or past
+// min(n, *ndev) is read or written.  force_hash (tests only, else null): item
+// i's hash instead of memo_hash of its tuple.
+struct MemoProbe {
+  const uint8_t *e, *r, *s;
+  const uint32_t* slot;
+  long n;
+  const uint32_t* ndev;
+  const KeyDesc* keys;
+  uint32_t nslots;
+  const uint32_t* young;
+  const uint32_t* old;
+  uint64_t entries;
+  uint8_t* status;
+  uint8_t *e_c, *r_c, *s_c;
+  uint32_t* slot_c;
+  uint32_t* origin;
+  uint32_t* miss;
+  uint64_t* stats;
+  const uint64_t* force_hash;
+};
+hipError_t memo_probe(const MemoProbe& p, hipStream_t st);
+// k_memo_commit, one compacted item per lane, j < min(n, *miss):
+// status[origin[j]] = status_c[j], and where that is MBFT_ACCEPT under a real
+// valid key the tuple is inserted into the young generation: an empty entry of
+// its probe sequence is claimed (0 -> busy by compare-and-swap), the payload
+// written, the ready tag published behind an agent-scope release.  No empty
+// entry in the sequence: the insert is dropped and counted, never an
+// overwrite.  force_hash: per COMPACTED item.
+struct MemoCommit {
+  const uint8_t *e_c, *r_c, *s_c;
+  const uint32_t* slot_c;
+  const uint32_t* origin;
+  const uint8_t* status_c;
+  long n;
+  const uint32_t* miss;
+  const KeyDesc* keys;
+  uint32_t nslots;
+  uint32_t* young;
+  uint64_t entries;
+  uint8_t* status;
+  uint64_t* stats;
+  const uint64_t* force_hash;
+};
+hipError_t memo_commit(const MemoCommit& c, hipStream_t st);
 // The key memory budget's ranking (key_rank.hip): every slot
 // ranked on the GPU by its use count, one slot per lane, grid-stride on
 // k_key_account's grid.  A slot's count u is the sum of its entry in the

@@ -60,6 +60,132 @@ int grow_key_counters(mbft_ctx* c) {
   return MBFT_OK;
 }
 
+// ------------------------------------------------------ the verified-call memo
+// (the shape and the rotation rule are memo_plan.h's.)
+
+// The clear a quiet memo was asked for (M.m held, inflight == 0, the memo's
+// device current): both generations where a clear is wanted, else the old one,
+// which then becomes the young.  The memset goes on st with ev_clear behind
+// it; the flags are lifted only where both were queued.  Returns the HIP
+// error where they were not: the flags stay and passes go on without the memo.
+static hipError_t memo_clear_quiet(VerifiedMemo& M, hipStream_t st) {
+  const size_t gen_bytes = (size_t)M.rot.entries * mbft::kMemoEntryBytes;
+  // (an earlier clear, on another stream, ends first: what follows this one is behind both)
+  hipError_t e = M.ev_pending ? hipStreamWaitEvent(st, M.ev_clear, 0) : hipSuccess;
+  if (e != hipSuccess) {
+  } else if (M.clear_wanted) {
+    e = hipMemsetAsync(M.tab, 0, 2 * gen_bytes, st);
+  } else {
+    const int old = M.rot.young ^ 1;
+    e = hipMemsetAsync(reinterpret_cast<uint8_t*>(M.tab) + (size_t)old * gen_bytes, 0, gen_bytes, st);
+  }
+  if (e == hipSuccess) e = hipEventRecord(M.ev_clear, st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return e;
+  }
+  M.ev_pending = true;
+  if (M.clear_wanted) {
+    M.rot.young_calls = 0;
+    M.clears++;
+  } else {
+    M.rot.rotate();
+  }
+  M.clear_wanted = M.rotate_wanted = false;
+  return hipSuccess;
+}
+
+bool memo_pass_begin(mbft_ctx* g, hipStream_t st, uint64_t calls, MemoView* v) {
+  VerifiedMemo* M = tabs(g)->memo;
+  if (!M || g->memo_guards <= 0) return false;
+  std::lock_guard<std::mutex> lk(M->m);
+  if (!M->tab || M->rotate_wanted || M->clear_wanted) return false;
+  if (M->ev_pending) {  // the last clear ran on another pass's stream
+    if (hipEventQuery(M->ev_clear) == hipSuccess) {
+      M->ev_pending = false;
+    } else {
+      (void)hipGetLastError();
+      if (hipStreamWaitEvent(st, M->ev_clear, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+      }
+    }
+  }
+  M->inflight++;
+  const size_t gen_words = (size_t)M->rot.entries * mbft::kMemoEntryWords;
+  v->young = M->tab + (size_t)M->rot.young * gen_words;
+  v->old = M->tab + (size_t)(M->rot.young ^ 1) * gen_words;
+  v->entries = M->rot.entries;
+  v->stats = M->d_stats;
+  g->memo_open.push_back(MemoOpen{M, st, calls});
+  return true;
+}
+
+void memo_pass_end(mbft_ctx* g) {
+  for (const MemoOpen& o : g->memo_open) {
+    // (the callers have synchronized already; after an error they may not have)
+    if (hipStreamSynchronize(o.st) != hipSuccess) (void)hipGetLastError();
+    std::lock_guard<std::mutex> lk(o.memo->m);
+    if (o.memo->rot.add(o.calls)) o.memo->rotate_wanted = true;
+    // (a clear that fails here leaves its flag set: the memo stays out of use and the next quiet moment tries again)
+    if (--o.memo->inflight == 0 && (o.memo->rotate_wanted || o.memo->clear_wanted))
+      (void)memo_clear_quiet(*o.memo, o.st);
+  }
+  g->memo_open.clear();
+}
+
+int memo_clear_engine(mbft_ctx* c, mbft_ctx* e) {
+  VerifiedMemo* M = e->memo;
+  if (!M) return MBFT_OK;
+  if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+  std::lock_guard<std::mutex> lk(M->m);
+  if (!M->tab) return MBFT_OK;
+  M->clear_wanted = true;
+  if (M->inflight == 0) {
+    HIPCHK(c, memo_clear_quiet(*M, e->kstream));
+    HIPCHK(c, hipStreamSynchronize(e->kstream));
+  }
+  return MBFT_OK;
+}
+
+// An empty table of two generations of `entries`, its counters and its event
+// into *M, on engine e's device (current).  On failure what was allocated
+// stays in *M for the caller to free.
+static int memo_fill(mbft_ctx* c, mbft_ctx* e, uint64_t entries, VerifiedMemo* M) {
+  const size_t bytes = 2 * (size_t)entries * mbft::kMemoEntryBytes;
+  M->rot.entries = entries;
+  if (hipMalloc(&M->tab, bytes) != hipSuccess ||
+      hipMalloc(&M->d_stats, mbft_launch::kMemoStats * sizeof(uint64_t)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, MBFT_ERR_NOMEM, "verified-call memo: out of device memory");
+  }
+  // (kstream: never the null stream, see host_internal.h)
+  HIPCHK(c, hipEventCreateWithFlags(&M->ev_clear, hipEventDisableTiming));
+  HIPCHK(c, hipMemsetAsync(M->tab, 0, bytes, e->kstream));
+  HIPCHK(c, hipMemsetAsync(M->d_stats, 0, mbft_launch::kMemoStats * sizeof(uint64_t), e->kstream));
+  HIPCHK(c, hipStreamSynchronize(e->kstream));
+  return MBFT_OK;
+}
+
+int memo_alloc_engine(mbft_ctx* c, mbft_ctx* e, uint64_t entries) {
+  if (hipSetDevice(e->device) != hipSuccess) return fail(c, MBFT_ERR_HIP, "hipSetDevice");
+  memo_free(e);
+  e->memo = new VerifiedMemo;
+  const int rc = memo_fill(c, e, entries, e->memo);
+  if (rc) memo_free(e);
+  return rc;
+}
+
+void memo_free(mbft_ctx* e) {
+  VerifiedMemo* M = e->memo;
+  if (!M) return;
+  if (M->tab) (void)hipFree(M->tab);
+  if (M->d_stats) (void)hipFree(M->d_stats);
+  if (M->ev_clear) (void)hipEventDestroy(M->ev_clear);
+  delete M;
+  e->memo = nullptr;
+}
+
 void count_resident_use(mbft_ctx* c, uint32_t slot, uint8_t status) {
   if (!c->accounting.load(std::memory_order_relaxed)) return;
   if (slot >= c->keydesc.size() || !c->keydesc[slot].valid) return;
@@ -233,6 +359,8 @@ int release_slots(mbft_ctx* c, const std::vector<uint32_t>& sl) {
     }
     if (const int rc = upload_keydesc(e)) return e == c ? rc : fail(c, rc, "peer engine: " + e->err);
     if (const int rc = quiesce(c, e)) return rc;
+    // a released number may come to mean another point: what the memo holds under it goes
+    if (const int rc = memo_clear_engine(c, e)) return rc;
     for (size_t j = 0; j < sl.size(); j++) {
       if (was[j].valid) {
         if (mbft::key_class_queued(was[j].wbits)) e->tfree_keys--;
@@ -508,6 +636,95 @@ int mbft_set_key_budget(mbft_ctx* c, uint64_t bytes) {
 int mbft_get_key_budget(const mbft_ctx* c, uint64_t* bytes) {
   if (!c || !bytes) return MBFT_ERR_ARG;
   *bytes = c->key_budget;
+  return MBFT_OK;
+}
+
+int mbft_set_verified_memo(mbft_ctx* c, uint64_t bytes) {
+  if (!c || c->owner) return MBFT_ERR_ARG;
+  const mbft::MemoGeometry geo = mbft::memo_geometry(bytes);
+  if (bytes != 0 && geo.entries == 0)
+    return fail(c, MBFT_ERR_ARG, "mbft_set_verified_memo: below the minimum of 2 x 1,024 entries");
+  KeyWriteGuard g(c);  // no pass is in flight
+  const std::vector<mbft_ctx*> eng = engines_of(c);
+  std::vector<VerifiedMemo*> fresh;
+  int rc = MBFT_OK;
+  if (bytes != 0) {
+    for (mbft_ctx* e : eng) {
+      if (hipSetDevice(e->device) != hipSuccess) {
+        rc = fail(c, MBFT_ERR_HIP, "hipSetDevice");
+        break;
+      }
+      VerifiedMemo* M = new VerifiedMemo;
+      fresh.push_back(M);
+      if ((rc = memo_fill(c, e, geo.entries, M)) != MBFT_OK) break;
+    }
+  }
+  // everything that can fail comes before the first engine changes: the streams
+  // that may still run a pass's kernels on an old memo have finished
+  for (size_t j = 0; j < eng.size() && !rc; j++) {
+    if (!eng[j]->memo) continue;
+    if (hipSetDevice(eng[j]->device) != hipSuccess)
+      rc = fail(c, MBFT_ERR_HIP, "hipSetDevice");
+    else
+      rc = sync_engine_streams(c, eng[j]);
+  }
+  if (rc) {  // the previous state stays
+    for (size_t j = 0; j < fresh.size(); j++) {
+      if (hipSetDevice(eng[j]->device) != hipSuccess) (void)hipGetLastError();
+      if (fresh[j]->tab) (void)hipFree(fresh[j]->tab);
+      if (fresh[j]->d_stats) (void)hipFree(fresh[j]->d_stats);
+      if (fresh[j]->ev_clear) (void)hipEventDestroy(fresh[j]->ev_clear);
+      delete fresh[j];
+    }
+    (void)hipSetDevice(c->device);
+    return rc;
+  }
+  for (size_t j = 0; j < eng.size(); j++) {
+    if (hipSetDevice(eng[j]->device) != hipSuccess) (void)hipGetLastError();
+    memo_free(eng[j]);
+    if (bytes != 0) eng[j]->memo = fresh[j];
+  }
+  (void)hipSetDevice(c->device);
+  return MBFT_OK;
+}
+
+int mbft_get_verified_memo(mbft_ctx* c, uint64_t* bytes) {
+  if (!c || c->owner || !bytes) return MBFT_ERR_ARG;
+  std::shared_lock<std::shared_mutex> t(c->tab_mu);
+  *bytes = c->memo ? 2u * c->memo->rot.entries * mbft::kMemoEntryBytes : 0u;
+  return MBFT_OK;
+}
+
+int mbft_verified_memo_stats(mbft_ctx* c, uint64_t out[6]) {
+  if (!c || c->owner || !out) return MBFT_ERR_ARG;
+  std::shared_lock<std::shared_mutex> t(c->tab_mu);
+  for (int k = 0; k < 6; k++) out[k] = 0;
+  for (mbft_ctx* e : engines_of(c)) {
+    VerifiedMemo* M = e->memo;
+    if (!M) continue;
+    if (hipSetDevice(e->device) != hipSuccess) return MBFT_ERR_HIP;
+    uint64_t v[mbft_launch::kMemoStats];
+    if (hipMemcpyAsync(v, M->d_stats, sizeof(v), hipMemcpyDeviceToHost, e->kstream) != hipSuccess ||
+        hipStreamSynchronize(e->kstream) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipSetDevice(c->device);
+      return MBFT_ERR_HIP;
+    }
+    for (int k = 0; k < mbft_launch::kMemoStats; k++) out[k] += v[k];
+    std::lock_guard<std::mutex> lk(M->m);
+    out[4] += M->rot.rotations;
+    out[5] += M->clears;
+  }
+  (void)hipSetDevice(c->device);
+  return MBFT_OK;
+}
+
+int mbft_clear_verified_memo(mbft_ctx* c) {
+  if (!c || c->owner) return MBFT_ERR_ARG;
+  std::shared_lock<std::shared_mutex> t(c->tab_mu);  // (the memo is not replaced meanwhile; passes go on)
+  for (mbft_ctx* e : engines_of(c))
+    if (const int rc = memo_clear_engine(c, e)) return rc;
+  (void)hipSetDevice(c->device);
   return MBFT_OK;
 }
 

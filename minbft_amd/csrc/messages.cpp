@@ -572,8 +572,10 @@ int run_message_calls(mbft_ctx* c, const mbft_message* msgs, size_t n,
                            st));
   HIPCHK(c, mbft_launch::authen_e(c->sha_out.as<uint8_t>(), c->b_desc.as<mbft::AuthenDesc>(),
                                   (long)nc, c->b_e.as<uint8_t>(), st));
+  const MemoPassGuard memo_guard(c);  // (ends the pass after the synchronize below)
   int rc = verify_device(c, c->b_e.as<uint8_t>(), c->b_r.as<uint8_t>(), c->b_s.as<uint8_t>(),
-                         c->b_slot.as<uint32_t>(), nc, c->b_status.as<uint8_t>(), st);
+                         c->b_slot.as<uint32_t>(), nc, c->b_status.as<uint8_t>(), st, /*host_status=*/false,
+                         /*latency=*/false, /*d_winv=*/nullptr, /*d_count=*/nullptr, /*memo=*/true);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(c->h_status.p, c->b_status.p, nc, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));

@@ -161,7 +161,7 @@ int check_one_wait(mbft_ctx* c, mbft_ctx* g, const mbft::MsgDevArgs& a, size_t n
   hipStream_t st = g->stream, vb = st;
   HIPCHK(g, mbft_launch::msg_calls(a, 0, (long)n, 0, (long)nc3, vb, bounds + 1, listed));
   int rc = verify_device(g, a.e, a.r, a.s, a.slot, nc3, dstatus, vb, /*host_status=*/true,
-                         /*latency=*/false, /*d_winv=*/nullptr, /*d_count=*/bounds + 1);
+                         /*latency=*/false, /*d_winv=*/nullptr, /*d_count=*/bounds + 1, /*memo=*/true);
   if (rc) return rc;
   HIPCHK(g, g->hm_pack.ensure(L.end));
   HIPCHK(g, hipMemcpyAsync(g->hm_pack.p, g->m_pack.p, L.end, hipMemcpyDeviceToHost, st));
@@ -175,6 +175,7 @@ int check_one_wait(mbft_ctx* c, mbft_ctx* g, const mbft::MsgDevArgs& a, size_t n
   }
   prof.done(sizeof(mbft_msg_rec) * n + nbytes);
   const size_t nc = reinterpret_cast<const uint32_t*>(hp + L.bounds)[1];
+  if (!g->memo_open.empty()) g->memo_open.back().calls = nc;  // (the memo's rotation rule: the count, not its bound)
   chk->n = n;
   chk->checks.resize(n);
   auto calls = std::make_shared<MsgCalls>();
@@ -195,6 +196,7 @@ int validate_flat_device_impl(mbft_ctx* c, mbft_ctx* g, const mbft_msg_rec* recs
                               const uint8_t* bytes, size_t nbytes, uint32_t n_replicas, uint32_t flags,
                               int32_t* out, mbft_msg_batch* chk, size_t abase) {
   const size_t up = nbytes - abase;  // arena bytes uploaded
+  const MemoPassGuard memo_guard(g);   // the pass's verifies may run under the verified-call memo
   const auto t0 = std::chrono::steady_clock::now();
   if (!g->pool) g->pool.reset(new Pool(pool_workers(g)));
   int rc = sync_keymap(c, g);
@@ -389,7 +391,7 @@ int validate_flat_device_impl(mbft_ctx* c, mbft_ctx* g, const mbft_msg_rec* recs
     if (cnt) {
       rc = verify_device(g, a.e + 32 * (size_t)base, a.r + 32 * (size_t)base, a.s + 32 * (size_t)base,
                          a.slot + base, cnt, dstatus + base, vb, /*host_status=*/true,
-                         /*latency=*/j1 == K - 1 && S >= 0);
+                         /*latency=*/j1 == K - 1 && S >= 0, /*d_winv=*/nullptr, /*d_count=*/nullptr, /*memo=*/true);
       if (rc) return rc;
     }
     base = end;

@@ -40,12 +40,22 @@ struct VerifyPlan {
                      // a key of that class exists; the exact-path queue's: the s^-1 kernels)
   bool account = false;  // k_key_account ends the batch: after the form's last kernel that writes a
                          // status (kLarge: after k_verify_slow and k_verify_ladder)
+  bool memo = false;  // the batch is the misses of a memo pass (memo_plan.h): k_memo_probe ran in front
+                      // of it over the original items and k_memo_commit follows it; the use-count
+                      // stage then runs over the ORIGINAL items, after the commit, not here
 };
 
 // The per-key use counts (mbft_set_key_accounting): the stage is part of the
 // plan, off unless the context asks for it.
 constexpr VerifyPlan verify_plan_account(VerifyPlan p, bool accounting) {
   p.account = accounting;
+  return p;
+}
+// The verified-call memo (mbft_set_verified_memo): likewise off unless the
+// pass runs under one.  The plan of the misses never accounts itself.
+constexpr VerifyPlan verify_plan_memo(VerifyPlan p, bool memo) {
+  p.memo = memo;
+  if (memo) p.account = false;
   return p;
 }
 // Its grid: one item per lane, 256 a block, grid-stride past kAccountBpc blocks
