@@ -1795,7 +1795,7 @@ MBFT_DEV void verify_pair(const VerifyArgs& A, long i, int half, bool in_batch, 
 // Chudnovsky addition on lanes 0 and 2 (never degenerate: with u = a + b the
 // low and high parts of a scalar in [1, N), a == -b mod N is u == 0, and a ==
 // b mod N needs u = 2 a + N with a the low part of u itself, which no window
-// size admits -- tests/test_gpu_parity.py checks it for W = 8..29; a zero part
+// size admits -- tests/test_quad_joins.py checks it for W = 4..29; a zero part
 // is infinity, flagged), then G and Q by the x-only addition on lane 0 (u1 G
 // == +-u2 Q takes the exact path, as in verify_pair).  Neither half of a range
 // degenerates: every partial sum of a range is a multiple of 2^(W lo), smaller
@@ -1929,7 +1929,8 @@ MBFT_DEV void verify_quad(const VerifyArgs& A, long i, int q, bool in_batch, uin
 // at once -- lane 4 j + q loads quarter q of window lo + j's 64-B entry into
 // the wave's LDS slice `pre` -- so the HBM (and TLB) latency of the random
 // 64-B reads is paid once instead of once per addition; windows past
-// kSplitPre (key windows below 16) load as they go.
+// kSplitPre (ranges of 19 to 32 windows: comb windows 4 to 7 split in two)
+// load as they go.
 #ifdef MBFT_SPLIT_TIMING
 // Phase timestamps of the last split / resident item of workgroups 0 and 1
 // (timing builds only, tools/split_timing.py, tools/resident_timing.py):

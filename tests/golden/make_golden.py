@@ -20,6 +20,8 @@ Fixtures:
                   digit recoding: the top window's last entry (digit 2^L),
                   the largest positive digit 2^(W-1), a zero digit that
                   still carries, small scalars.
+  small_windows.json  the same corners, every range seam of the verify forms
+                  and accumulator collisions for the 4..7-bit windows.
   der.json        DER signature strings -> Go encoding/asn1 outcome.
   authen.json     Authenticator-level call sequences (ECDSA roles with the
                   Sum(m) quirk, USIG roles with epoch capture), with the
@@ -125,12 +127,17 @@ def signed_digits(u, W):
     return out
 
 
-def comb_collision(i, infinity, W=8, rng=None):
+def comb_collision(i, infinity, W=8, rng=None, max_draws=None):
     """Accepting instance where, in the comb's Q phase, the accumulator hits
     +addend (doubling) or -addend (infinity) at window i (W-bit signed-digit
-    windows, processed low to high, after all G windows)."""
+    windows, processed low to high, after all G windows).  max_draws: give up
+    (None) after that many draws (a draw whose digit i is zero is repeated)."""
     rs = (lambda: rng.randrange(1, o.N)) if rng is not None else rand_scalar
+    draws = 0
     while True:
+        draws += 1
+        if max_draws is not None and draws > max_draws:
+            return None
         k = rs()
         R = o.scalar_mult(k, o.G)
         r = R[0] % o.N
@@ -327,6 +334,182 @@ def make_scalar_edges():
             out.append(vec(q, e ^ 1, r, s, lab + "_tampered"))
             assert (out[-2]["expect"], out[-1]["expect"]) == (1, 0), lab
     assert len(out) == 54
+    return out
+
+
+SMALL_WINDOWS = (4, 5, 6, 7)
+
+
+def small_window_seams(W):
+    """The window indices at which some verify form starts a range of a
+    W-bit comb or leaves the LDS preload (kernels.hip: kSplitPre = 16 windows
+    from a range's start): the split and resident one-workgroup forms and the
+    quads' lanes split at mid, the resident two-workgroup form at j S / 4,
+    the pairs' and quads' generator lanes start at window 2 after the
+    affine + affine pair."""
+    S = -(-256 // W)
+    mid = (S + 1) // 2
+    starts = [0, mid] + [j * S // 4 for j in (1, 2, 3)]
+    return sorted(set(starts + [k + 16 for k in starts if k + 16 < S] + [2]))
+
+
+def small_window_range_starts(W):
+    """The seams that start a range (comb_range_uniform's first pair)."""
+    S = -(-256 // W)
+    return sorted({0, (S + 1) // 2} | {j * S // 4 for j in (1, 2, 3)})
+
+
+def small_window_scalars(W, rng):
+    """The crafted scalars of one window size, as (name, roles, u): each is
+    checked here for the digit property its name states."""
+    S = -(-256 // W)
+    L = 256 - (S - 1) * W
+    mid = (S + 1) // 2
+    half = 1 << (W - 1)
+    ones = (1 << W) - 1
+    ALL, U2 = ("u1", "u2", "both"), ("u2",)
+
+    def join(win):
+        assert len(win) == S and all(0 <= v <= ones for v in win) and win[-1] < 1 << L
+        u = sum(v << (W * i) for i, v in enumerate(win))
+        assert 0 < u < o.N, (W, win)
+        return u
+
+    def base():
+        # windows in [1, 2^(W-1)): every digit is its window, no carry anywhere
+        # (and u < N: the top bit of window S - 2 is clear)
+        return [rng.randrange(1, half) for _ in range(S - 1)] + [rng.randrange(1, 1 << L)]
+
+    out = []
+    u = o.N - 1 - rng.randrange(1 << 200)
+    assert signed_digits(u, W)[-1] == 1 << L
+    out.append(("top_rnd", ALL, u))
+    for name, roles, v in (("half", ALL, half), ("halfp1", U2, half + 1), ("halfm1", U2, half - 1)):
+        u = join([v] * (S - 1) + [v & ((1 << L) - 1)])
+        dig = signed_digits(u, W)[:-1]
+        if name == "half":      # the largest positive digit, not recoded
+            assert dig == [half] * (S - 1)
+        elif name == "halfp1":  # every digit negative, every window carries
+            assert all(-half < d < 0 for d in dig)
+        else:
+            assert dig == [half - 1] * (S - 1)
+        out.append((name, roles, u))
+    for k in small_window_seams(W):
+        assert k + 1 < S
+        if k > 0:
+            # all-ones windows up to k - 1: digit -1, then zero digits that
+            # carry, and the carry enters window k
+            win = base()
+            for j in range(max(0, k - 3), k):
+                win[j] = ones
+            dig = signed_digits(join(win), W)
+            assert dig[k] == win[k] + 1 and dig[k - 1] == (-1 if k - 1 == max(0, k - 3) else 0)
+            out.append(("seam%d_carry" % k, ALL, join(win)))
+            win = base()
+            win[k - 1] = win[k] = half
+            dig = signed_digits(join(win), W)
+            assert dig[k - 1] == dig[k] == half and dig[k + 1] == win[k + 1]
+            out.append(("seam%d_half" % k, U2, join(win)))
+        # zero digits at the seam: (zero, non-zero), (zero, zero) and, where a
+        # range starts (its first pair of windows is one addition),
+        # (non-zero, zero)
+        for name, z in (("z0", (k,)), ("z01", (k, k + 1)), ("z1", (k + 1,))):
+            if name == "z1" and k not in small_window_range_starts(W):
+                continue
+            win = base()
+            for j in z:
+                win[j] = 0
+            dig = signed_digits(join(win), W)
+            assert [dig[j] == 0 for j in (k, k + 1)] == [j in z for j in (k, k + 1)]
+            assert k == 0 or dig[k - 1] != 0
+            out.append(("seam%d_%s" % (k, name), U2, join(win)))
+    win = base()
+    win[mid:] = [0] * (S - mid)
+    assert signed_digits(join(win), W)[mid:] == [0] * (S - mid) and join(win) < 1 << (W * mid)
+    out.append(("low_only", U2, join(win)))
+    win = base()
+    win[:mid] = [0] * mid
+    assert signed_digits(join(win), W)[:mid] == [0] * mid and join(win) % (1 << (W * mid)) == 0
+    out.append(("high_only", U2, join(win)))
+    return out
+
+
+def make_small_windows():
+    """Crafted vectors for the key and generator windows 4 to 7 (S = 64, 52,
+    43, 37 windows a scalar), in make_scalar_edges' construction -- chosen
+    (u1, u2) under one key, each accepting vector followed by the same with
+    e ^ 1 -- labelled w<W>:<name>:<role>, or any:... where the property holds
+    at every window, with ":bad" on the rejecting twin:
+
+      any   N - 1 (the top window's last entry, digit 2^L), 2^255 - 1
+            (digit -1, zero digits that carry, the top), 1, 2;
+      w<W>  a random scalar in [N - 2^200, N); every window 2^(W-1), 2^(W-1)
+            + 1, 2^(W-1) - 1; at every seam k of small_window_seams(W): a
+            carry entering window k after all-ones windows, digit 2^(W-1) at
+            k - 1 and k, zero digits at k, at k and k + 1 and (range starts)
+            at k + 1 only; a scalar whose windows from mid on are zero, and
+            one whose windows below mid are;
+      w<W>:comb_dbl<i> / comb_inf<i>  accumulator collisions (comb_collision)
+            at windows 0, 1, 2, mid - 1, mid, S - 2, S - 1 (no infinity case
+            at the last).
+
+    The full cross product with three roles is twice the size cap of a
+    golden file (prehashed.json's 224,121 bytes), so: u1, u2 and both for the
+    top, every-window-2^(W-1) and seam-carry scalars, u2 alone (the scalar an
+    attacker picks) for the rest; the carry and 2^(W-1) scalars need a window
+    k - 1 and are left out at seam 0; (non-zero, zero) only where a range
+    starts; the collisions without a rejecting twin (as in prehashed.json
+    and comb_windows.json: with e ^ 1 they are no collisions any more, only
+    one more random reject), and the file one vector per line without
+    spaces.  5 + 8 + 10 + 10 = 33 seams; 492 crafted vectors, half of them
+    accepting (any 12, w4 80, w5 116, w6 142, w7 142), and 4 x 13 collisions:
+    544 vectors, 217 KB.  Own RNG stream."""
+    rng = random.Random(0x534D414C)  # "SMAL"
+    d = key_from_seed(0)
+    q = o.pubkey(d)
+    out = []
+
+    def craft(prefix, name, roles, u):
+        for role in roles:
+            u1 = u if role != "u2" else rng.randrange(1, o.N)
+            u2 = u if role != "u1" else rng.randrange(1, o.N)
+            R = o.scalar_mult((u1 + u2 * d) % o.N, o.G)
+            assert R is not None
+            r = R[0] % o.N
+            assert r != 0
+            s = r * pow(u2, -1, o.N) % o.N
+            e = u1 * s % o.N
+            lab = "%s:%s:%s" % (prefix, name, role)
+            out.append(vec(q, e, r, s, lab))
+            out.append(vec(q, e ^ 1, r, s, lab + ":bad"))
+            assert (out[-2]["expect"], out[-1]["expect"]) == (1, 0), lab
+
+    ALL, U2 = ("u1", "u2", "both"), ("u2",)
+    ones_carry = (1 << 255) - 1
+    for W in SMALL_WINDOWS:
+        S = -(-256 // W)
+        L = 256 - (S - 1) * W
+        assert signed_digits(o.N - 1, W)[-1] == 1 << L
+        dig = signed_digits(ones_carry, W)
+        assert dig[:-1] == [-1] + [0] * (S - 2) and dig[-1] == ((1 << (L - 1)) if L > 1 else 1)
+    for name, roles, u in (("top_Nm1", ALL, o.N - 1), ("ones_carry", U2, ones_carry), ("one", U2, 1),
+                           ("two", U2, 2)):
+        craft("any", name, roles, u)
+    for W in SMALL_WINDOWS:
+        for name, roles, u in small_window_scalars(W, rng):
+            craft("w%d" % W, name, roles, u)
+        S = -(-256 // W)
+        mid = (S + 1) // 2
+        for i in (0, 1, 2, mid - 1, mid, S - 2, S - 1):
+            for inf in ((False, True) if i < S - 1 else (False,)):
+                got = comb_collision(i, inf, W, rng, max_draws=64)
+                lab = "w%d:comb_%s%d" % (W, "inf" if inf else "dbl", i)
+                if got is None:
+                    print("small_windows: no non-zero digit for", lab, file=sys.stderr)
+                    continue
+                qq, e, r, s = got
+                out.append(vec(qq, e, r, s, lab))
+                assert out[-1]["expect"] == 1, lab
     return out
 
 
@@ -647,15 +830,20 @@ def make_messages():
 
 
 def main():
-    def dump(name, obj):
+    def dump(name, obj, rows=False):
         with open(os.path.join(HERE, name), "w") as f:
-            json.dump(obj, f, indent=0, sort_keys=True)
+            if rows:  # a list, one element per line without spaces: ~4 % smaller
+                f.write("[\n" + ",\n".join(json.dumps(v, sort_keys=True, separators=(",", ":"))
+                                           for v in obj) + "\n]")
+            else:
+                json.dump(obj, f, indent=0, sort_keys=True)
             f.write("\n")
 
     dump("kat.json", make_kat())
     dump("prehashed.json", make_prehashed())
     dump("comb_windows.json", make_comb_windows())
     dump("scalar_edges.json", make_scalar_edges())
+    dump("small_windows.json", make_small_windows(), rows=True)
     dump("der.json", make_der())
     a = make_authen()
     expected_authen(a)

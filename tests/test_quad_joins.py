@@ -2,7 +2,7 @@
 low and high halves of one scalar's signed-digit comb windows never meet in
 a degenerate addition.  With u = a + b (a: windows [0, mid), b: [mid, S)),
 a == -b (mod N) only for u == 0, and a == b (mod N) needs u = 2 a + N with a
-the low part of u itself; no window size 8..29 admits one.  Pure Python over
+the low part of u itself; no window size 4..29 admits one.  Pure Python over
 the kernel's recoding (comb_digit), no GPU."""
 import random
 
@@ -29,7 +29,7 @@ def split(u, W):
     return a, b, mid
 
 
-@pytest.mark.parametrize("W", list(range(8, 30)))
+@pytest.mark.parametrize("W", list(range(4, 30)))
 def test_halves_sum_to_the_scalar(W):
     rng = random.Random(W)
     for u in [1, 2, N - 1, N - 2, (1 << 255) + 7] + [rng.randrange(1, N) for _ in range(200)]:
@@ -39,7 +39,7 @@ def test_halves_sum_to_the_scalar(W):
         assert abs(a) <= 1 << (W * mid)
 
 
-@pytest.mark.parametrize("W", list(range(8, 30)))
+@pytest.mark.parametrize("W", list(range(4, 30)))
 def test_no_degenerate_half_join(W):
     S = (256 + W - 1) // W
     mid = (S + 1) // 2
