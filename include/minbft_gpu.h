@@ -611,6 +611,51 @@ int mbft_verify_prehashed_device(mbft_ctx* ctx, const uint8_t* d_e, const uint8_
                                  const uint8_t* d_s, const uint32_t* d_slots, size_t n,
                                  uint8_t* d_status, void* hip_stream);
 
+/* The inline-key class: verify under keys GIVEN WITH THE CALL, no slot, no
+ * registration (the coldest rung of the key ladder: zero bytes, zero state).
+ * This is the reference's own boundary -- crypto/ecdsa.Verify(pub, hash, r, s)
+ * at sample/authentication/crypto.go:86 and usig/sgx/usig-enclave.go:224, and
+ * AuthenticationScheme.VerifyAuthenticationTag(m, sig, pubKey) at
+ * crypto.go:95-98 and 120-126 take the key per call.
+ *
+ * mbft_verify_prehashed_keys / _device: xy is n x 64 bytes, big-endian
+ * X || Y, as mbft_register_points takes them; e, r, s as above.  status[i] is
+ * exactly what mbft_verify_prehashed returns for (e, r, s)[i] under a slot that
+ * mbft_register_points gave xy[i]: MBFT_ACCEPT or MBFT_REJECT_SIG for a valid
+ * point; MBFT_BAD_KEY for X >= p, Y >= p or a point off the curve ((0, 0)
+ * among them), also where r or s is out of range; MBFT_REJECT_SIG for a valid
+ * point with r or s outside [1, N).  Each point is validated on the GPU, then
+ * used by the table-free keys' ladder: every degenerate case is exact.
+ *
+ * mbft_scheme_verify_flat32: PublicAuthenScheme.VerifyAuthenticationTag(m, sig,
+ * pk) of the ECDSA roles (crypto.go:120-126 -> 79-89), n calls: call i =
+ * (msgs[msg_off[i] .. msg_off[i+1]), tags[tag_off[i] .. tag_off[i+1]),
+ * xy[64 i ..]).  e = (m || SHA256(""))[0:32] (crypto.go:121; messages shorter
+ * than 32 bytes and empty ones included); the tag by mbft_der_parse_sig's
+ * rules: a parse error is MBFT_MALFORMED_DER (where Go panics) and wins over
+ * MBFT_BAD_KEY, bytes after the SEQUENCE are ignored, an r or s outside
+ * (0, 2^256) goes to the verifier as zero and is rejected there.  The host
+ * decodes; only the undecided calls go to the GPU.  There is no USIG form
+ * (that scheme keeps epoch state per key fingerprint).
+ *
+ * n == 0 returns MBFT_OK; a NULL buffer with n > 0 is MBFT_ERR_ARG.  The calls
+ * read the context's generator table and nothing else: they work on a context
+ * with no key at all, under any key class and generator window, and leave
+ * slots, key memory, use counts and the verified-call memo untouched.  They
+ * serialise on the context like mbft_verify_prehashed* and run on its own
+ * device.  The _device form is asynchronous on hip_stream (NULL: the
+ * context's).  Device pointers d_e, d_r, d_s and d_xy must be 16-byte aligned
+ * (the kernels read them as 128-bit words) -- what the mbft_verify_prehashed_device
+ * form requires of d_e, d_r, d_s as well. */
+int mbft_verify_prehashed_keys(mbft_ctx* ctx, const uint8_t* e, const uint8_t* r, const uint8_t* s,
+                               const uint8_t* xy, size_t n, uint8_t* status);
+int mbft_verify_prehashed_keys_device(mbft_ctx* ctx, const uint8_t* d_e, const uint8_t* d_r,
+                                      const uint8_t* d_s, const uint8_t* d_xy, size_t n,
+                                      uint8_t* d_status, void* hip_stream);
+int mbft_scheme_verify_flat32(mbft_ctx* ctx, const uint8_t* msgs, const uint32_t* msg_off,
+                              const uint8_t* tags, const uint32_t* tag_off, const uint8_t* xy,
+                              size_t n, uint8_t* status_out);
+
 /* Bulk ECDSA signing over decoded digests, for synthetic load generation
  * and tests (the signature format of crypto.go:63-76).  priv32: nkeys x 32 B
  * big-endian scalars; key_idx: n indices (NULL = key 0); e: n x 32 B; r, s:

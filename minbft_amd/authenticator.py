@@ -722,6 +722,46 @@ class Authenticator:
             ctypes.c_void_p(d_slots), n, ctypes.c_void_p(d_status), ctypes.c_void_p(stream)),
             "verify_prehashed_device")
 
+    # The inline-key class (include/minbft_gpu.h): the key is
+    # given with each item, nothing is registered and nothing of the key store
+    # is read or written.
+    def verify_prehashed_keys(self, e: np.ndarray, r: np.ndarray, s: np.ndarray,
+                              xy: np.ndarray) -> np.ndarray:
+        """mbft_verify_prehashed_keys: xy n x 64 bytes, big-endian X || Y, item
+        i's own key (validated on the GPU: a bad point reads BAD_KEY)."""
+        e = np.ascontiguousarray(e, dtype=np.uint8).reshape(-1, 32)
+        r = np.ascontiguousarray(r, dtype=np.uint8).reshape(-1, 32)
+        s = np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 32)
+        xy = np.ascontiguousarray(xy, dtype=np.uint8).reshape(-1, 64)
+        n = e.shape[0]
+        assert r.shape[0] == n and s.shape[0] == n and xy.shape[0] == n
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.mbft_verify_prehashed_keys(self.ctx, _buf(e), _buf(r), _buf(s), _buf(xy),
+                                                        n, _buf(out)), "verify_prehashed_keys")
+        return out
+
+    def verify_prehashed_keys_device(self, d_e: int, d_r: int, d_s: int, d_xy: int, n: int,
+                                     d_status: int, stream: int = 0) -> None:
+        self._check(self.lib.mbft_verify_prehashed_keys_device(
+            self.ctx, ctypes.c_void_p(d_e), ctypes.c_void_p(d_r), ctypes.c_void_p(d_s),
+            ctypes.c_void_p(d_xy), n, ctypes.c_void_p(d_status), ctypes.c_void_p(stream)),
+            "verify_prehashed_keys_device")
+
+    def scheme_verify(self, items) -> np.ndarray:
+        """mbft_scheme_verify_flat32 over calls (msg, tag, xy64): the ECDSA
+        scheme's VerifyAuthenticationTag(m, sig, pk) with the key per call."""
+        n = len(items)
+        out = np.zeros(n, dtype=np.uint8)
+        if n == 0:
+            self._check(self.lib.mbft_scheme_verify_flat32(self.ctx, None, None, None, None, None, 0,
+                                                           _buf(out)), "scheme_verify")
+            return out
+        _, _, mb, mo, tb, to = flat_calls([(0, 0, m, t) for (m, t, _) in items], compact=True)
+        xy = np.frombuffer(b"".join(bytes(q) for (_, _, q) in items), dtype=np.uint8).reshape(n, 64)
+        self._check(self.lib.mbft_scheme_verify_flat32(self.ctx, _buf(mb), _buf(mo), _buf(tb), _buf(to),
+                                                       _buf(xy), n, _buf(out)), "scheme_verify")
+        return out
+
     def sign_prehashed(self, priv: np.ndarray, e: np.ndarray,
                        key_idx: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         priv = np.ascontiguousarray(priv, dtype=np.uint8).reshape(-1, 32)

@@ -501,6 +501,22 @@ static size_t lane_inv_max_env() {
   return v;
 }
 
+// *idle (true on entry unless the caller rules it out): whether every earlier
+// batch of this engine has finished -- which of the batched s^-1 forms a batch
+// takes (verify_device_run).  MBFT_NINV=local answers yes without asking.
+static int batches_idle(mbft_ctx* c, bool* idle) {
+  if (*idle && !mbft::env_is("MBFT_NINV", "local"))
+    for (int j = 0; j < mbft_ctx::kPipe && *idle; j++) {
+      const hipError_t q = hipEventQuery(c->ev_done[j]);
+      if (q == hipErrorNotReady) {
+        *idle = false;
+      } else if (q != hipSuccess) {
+        return hip_fail(c, q, "hipEventQuery(ev_done)");
+      }
+    }
+  return MBFT_OK;
+}
+
 // Verify n decoded items (device pointers) -> device status, on stream st.
 // memo_misses: the items are the misses of a memo pass (verify_device below):
 // the plan does not account, the pass does over its original items.
@@ -578,15 +594,7 @@ static int verify_device_run(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r
   // behind) takes form 1 in any case, once buffer k is free.
   const bool levels = mbft::env_is("MBFT_NINV", "levels");
   bool idle = !levels;
-  if (idle && !mbft::env_is("MBFT_NINV", "local"))
-    for (int j = 0; j < mbft_ctx::kPipe && idle; j++) {
-      const hipError_t q = hipEventQuery(c->ev_done[j]);
-      if (q == hipErrorNotReady) {
-        idle = false;
-      } else if (q != hipSuccess) {
-        return hip_fail(c, q, "hipEventQuery(ev_done)");
-      }
-    }
+  if (const int rc = batches_idle(c, &idle)) return rc;
   if (latency && !idle) {
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // winv[k] / slowq[k] reuse
     idle = true;
@@ -684,6 +692,63 @@ int verify_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uin
     HIPCHK(c, mbft_launch::key_account(ka, st));
   }
   HIPCHK(c, hipEventRecord(c->ev_done[k], st));  // (again: memo_scr[k] is read until here)
+  return MBFT_OK;
+}
+
+// The inline-key class: n items whose keys stand beside them
+// (d_xy, n x 64 B big-endian) -> device status, on stream st.  Reads the
+// generator table and nothing else of the context: no slot, no descriptor, no
+// use count, no memo.  The buffer discipline is verify_device_run's: buffer k
+// of the rotation (its s^-1 planes, where the plan takes planes), free once
+// ev_done[k] has passed, marked done again behind the kernel.
+static int verify_keys_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r, const uint8_t* d_s,
+                              const uint8_t* d_xy, size_t n, uint8_t* d_status, hipStream_t st) {
+  if (n == 0) return MBFT_OK;
+  const mbft_ctx* tb = tabs(c);
+  const int k = c->pipe;
+  c->pipe = (k + 1) % mbft_ctx::kPipe;
+  const mbft::KeysPlan plan = mbft::verify_keys_plan((long)n, lane_inv_max_env(), mbft_launch::device_cus());
+  uint32_t* winv = nullptr;
+  if (!plan.lane_inv) {
+    HIPCHK(c, c->winv[k].ensure((size_t)9 * n * 4));
+    winv = c->winv[k].as<uint32_t>();
+    // the batched s^-1 as verify_device_run picks it: one launch per workgroup
+    // chain on an idle engine, the per-wave form beside batches in flight
+    bool idle = !mbft::env_is("MBFT_NINV", "levels");
+    if (const int rc = batches_idle(c, &idle)) return rc;
+    HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // winv[k] reuse
+    if (idle)
+      HIPCHK(c, mbft_launch::batch_inverse_s_local(d_s, (long)n, winv, nullptr, st));
+    else
+      HIPCHK(c, mbft_launch::batch_inverse_s_pipelined(d_s, (long)n, winv, nullptr, st));
+  } else {
+    HIPCHK(c, hipStreamWaitEvent(st, c->ev_done[k], 0));  // (ev_done[k] is recorded again below)
+  }
+  const mbft_launch::KeysBatch kb{d_e, d_r, d_s, d_xy, (long)n, d_status, winv};
+  HIPCHK(c, mbft_launch::verify_keys(kb, tb->d_tabG, tb->g_wbits, plan, st));
+  HIPCHK(c, hipEventRecord(c->ev_done[k], st));
+  return MBFT_OK;
+}
+
+// Host buffers in, host status out, on the context's own engine (not sharded
+// over peer engines).
+static int verify_keys_host(mbft_ctx* c, const uint8_t* e, const uint8_t* r, const uint8_t* s, const uint8_t* xy,
+                     size_t n, uint8_t* status) {
+  if (n == 0) return MBFT_OK;
+  HIPCHK(c, c->e.ensure(32 * n));
+  HIPCHK(c, c->r.ensure(32 * n));
+  HIPCHK(c, c->s.ensure(32 * n));
+  HIPCHK(c, c->xy.ensure(64 * n));
+  HIPCHK(c, c->status.ensure(n));
+  HIPCHK(c, hipMemcpyAsync(c->e.p, e, 32 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->r.p, r, 32 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->s.p, s, 32 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->xy.p, xy, 64 * n, hipMemcpyHostToDevice, c->stream));
+  if (const int rc = verify_keys_device(c, c->e.as<uint8_t>(), c->r.as<uint8_t>(), c->s.as<uint8_t>(),
+                                        c->xy.as<uint8_t>(), n, c->status.as<uint8_t>(), c->stream))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(status, c->status.p, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return MBFT_OK;
 }
 
@@ -1314,6 +1379,73 @@ int mbft_verify_prehashed_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t*
   if (c->slots.empty()) return fail(c, MBFT_ERR_STATE, "no keys registered");
   hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
   return verify_device(c, d_e, d_r, d_s, d_slots, n, d_status, st);
+}
+
+int mbft_verify_prehashed_keys(mbft_ctx* c, const uint8_t* e, const uint8_t* r, const uint8_t* s,
+                               const uint8_t* xy, size_t n, uint8_t* status) {
+  if (!c || (n && (!e || !r || !s || !xy || !status))) return MBFT_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (hipSetDevice(c->device) != hipSuccess) return MBFT_ERR_HIP;
+  return verify_keys_host(c, e, r, s, xy, n, status);
+}
+
+int mbft_verify_prehashed_keys_device(mbft_ctx* c, const uint8_t* d_e, const uint8_t* d_r,
+                                      const uint8_t* d_s, const uint8_t* d_xy, size_t n,
+                                      uint8_t* d_status, void* hip_stream) {
+  if (!c || (n && (!d_e || !d_r || !d_s || !d_xy || !d_status))) return MBFT_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (hipSetDevice(c->device) != hipSuccess) return MBFT_ERR_HIP;
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+  return verify_keys_device(c, d_e, d_r, d_s, d_xy, n, d_status, st);
+}
+
+// PublicAuthenScheme.VerifyAuthenticationTag(m, sig, pk), n calls: the host
+// decodes in the role path's order (DER, then the key -- which the GPU
+// validates), compacts the undecided calls and verifies them under their
+// inline keys.
+int mbft_scheme_verify_flat32(mbft_ctx* c, const uint8_t* msgs, const uint32_t* msg_off,
+                              const uint8_t* tags, const uint32_t* tag_off, const uint8_t* xy,
+                              size_t n, uint8_t* status_out) {
+  if (!c || (n && (!msg_off || !tag_off || !xy || !status_out))) return MBFT_ERR_ARG;
+  if (n == 0) return MBFT_OK;
+  if ((!msgs && msg_off[n] != msg_off[0]) || (!tags && tag_off[n] != tag_off[0])) return MBFT_ERR_ARG;
+  std::vector<uint8_t> e, r, s, q, st;
+  std::vector<size_t> origin;
+  e.reserve(32 * n);
+  r.reserve(32 * n);
+  s.reserve(32 * n);
+  q.reserve(64 * n);
+  origin.reserve(n);
+  for (size_t i = 0; i < n; i++) {
+    if (msg_off[i + 1] < msg_off[i] || tag_off[i + 1] < tag_off[i]) return MBFT_ERR_ARG;
+    const size_t msg_len = msg_off[i + 1] - msg_off[i], tag_len = tag_off[i + 1] - tag_off[i];
+    uint8_t r32[32], s32[32], e32[32];
+    size_t consumed = 0;
+    // crypto.go:79-89: DER first (Go panics on error); bytes after the SEQUENCE are ignored
+    if (!mbft_der_parse_sig(tag_len ? tags + tag_off[i] : nullptr, tag_len, r32, s32, &consumed)) {
+      status_out[i] = MBFT_MALFORMED_DER;
+      continue;
+    }
+    // md = msg || SHA256("") (crypto.go:121); e = left-most 32 bytes
+    const size_t k0 = msg_len < 32 ? msg_len : 32;
+    if (k0) memcpy(e32, msgs + msg_off[i], k0);
+    if (k0 < 32) memcpy(e32 + k0, kEmptyHash, 32 - k0);
+    e.insert(e.end(), e32, e32 + 32);
+    r.insert(r.end(), r32, r32 + 32);
+    s.insert(s.end(), s32, s32 + 32);
+    q.insert(q.end(), xy + 64 * i, xy + 64 * i + 64);
+    origin.push_back(i);
+  }
+  const size_t m = origin.size();
+  if (m == 0) return MBFT_OK;
+  st.resize(m);
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return MBFT_ERR_HIP;
+    if (const int rc = verify_keys_host(c, e.data(), r.data(), s.data(), q.data(), m, st.data())) return rc;
+  }
+  for (size_t j = 0; j < m; j++) status_out[origin[j]] = st[j];
+  return MBFT_OK;
 }
 
 int mbft_sign_prehashed(mbft_ctx* c, const uint8_t* priv32, size_t nkeys,

@@ -377,6 +377,19 @@ hipError_t key_pick_cold(const KeyRank& r, uint64_t max_uses, uint32_t* list, ui
 // MBFT_SPLIT_MAX (default 256; 0 disables the split form), read once.
 long split_max_env();
 hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const mbft::VerifyPlan& plan, hipStream_t st);
+// The inline-key form (k_verify_keys): n items whose keys
+// stand beside them, xy n x 64 B big-endian X || Y, validated by the kernel.
+// winv: 9 planes of n where the plan reads s^-1 from planes, else unused.  e,
+// r, s and xy are 16-byte aligned.  Reads the generator table and nothing else.
+struct KeysBatch {
+  const uint8_t *e, *r, *s, *xy;
+  long n;
+  uint8_t* status;
+  const uint32_t* winv;
+};
+// the device's compute units (what verify_keys_plan and the capped grids take)
+int device_cus();
+hipError_t verify_keys(const KeysBatch& b, const uint32_t* tabG, int wg, const mbft::KeysPlan& plan, hipStream_t st);
 // The resident verifier: one 256-thread workgroup per mailbox slot, or two
 // (`two`: one per scalar, each on its own CU).
 hipError_t verify_server(const mbft::ServerArgs& a, int servers, bool two, hipStream_t st);

@@ -10,6 +10,8 @@
 //              no doublings), entries gathered cooperatively into LDS;
 //              accept iff R != inf and x(R) mod N == r, checked
 //              projectively (X == r*Z^2 or X == (r+N)*Z^2), no inversion.
+//   k_verify_keys  the same check under keys given with the call (no slot):
+//              the point validated per lane, then the table-free ladder.
 // Table construction (init time, once per key; replica set is static):
 //   k_check_points, k_table_pow2, k_table_fill.
 // Batched scalar inversion (Montgomery's trick over strided groups):
@@ -2598,6 +2600,83 @@ __global__ void __launch_bounds__(256, 2) k_verify_ladder(VerifyArgs A) {
     verify_ladder_item<false>(A, (long)ladder_queue(A)[q]);
 }
 
+// The inline-key class (mbft_verify_prehashed_keys*): the key
+// arrives beside the signature, no slot, no KeyDesc, nothing of the key store.
+// Its own argument block -- VerifyArgs stays what it is.
+struct KeysArgs {
+  const uint8_t* e;        // n x 32 B big-endian
+  const uint8_t* r;
+  const uint8_t* s;
+  const uint8_t* xy;       // n x 64 B big-endian X || Y (crypto/ecdsa.Verify's pub, per item)
+  const uint32_t* winv;    // s^-1 R mod N, 9 planes of n (LANE_INV false), else null
+  const uint32_t* tabG;    // generator comb table (window wg)
+  int wg;
+  long n;
+  uint8_t* status;
+};
+
+// One item per lane, grid-stride, no LDS, no queue.  Per item: r, s in
+// [1, N); X, Y < p and Y^2 == X^3 - 3 X + b (k_check_points' field
+// operations, on the batch's own bytes); a dead item's status at once, a bad
+// key before a bad range (admit's precedence); else u2 Q by the ladder over
+// the validated point and u1 G's comb entries added with complete additions,
+// exactly verify_ladder_item's sum.  Lanes past n touch nothing.
+template <bool LANE_INV>
+__global__ void __launch_bounds__(256, 2) k_verify_keys(KeysArgs K) {
+  // what load_scalars and verify_finish_jac read of a batch
+  VerifyArgs A{};
+  A.e = K.e;
+  A.r = K.r;
+  A.s = K.s;
+  A.winv = K.winv;
+  A.n = K.n;
+  A.status = K.status;
+  const long stride = (long)gridDim.x * blockDim.x;
+#pragma unroll 1
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < K.n; i += stride) {
+    fe qx, qy;
+    bool key_ok, range_ok;
+    {
+      uint32_t rw[8], sw[8], wx[8], wy[8];
+      load_be256(rw, K.r + 32 * i);
+      load_be256(sw, K.s + 32 * i);
+      load_be256(wx, K.xy + 64 * i);
+      load_be256(wy, K.xy + 64 * i + 32);
+      range_ok = !words_is_zero(rw) && words_lt(rw, kNw) && !words_is_zero(sw) && words_lt(sw, kNw);
+      const bool in_range = words_lt(wx, kPw) && words_lt(wy, kPw);
+      fe b, t, lhs, rhs;
+      fe_from_words(qx, wx);
+      fe_from_words(qy, wy);
+      fe_from_words(b, kBw);
+      fe_to_mont(qx, qx);
+      fe_to_mont(qy, qy);
+      fe_to_mont(b, b);
+      fe_sqr(lhs, qy);
+      fe_sqr(t, qx);
+      fe_mul(t, t, qx);               // x^3
+      fe_mulsmall(rhs, qx, 3);
+      fe_sub(rhs, t, rhs);            // x^3 - 3x
+      fe_add(rhs, rhs, b);
+      fe_canon(lhs);
+      fe_canon(rhs);
+      key_ok = in_range && fe_eq_canon(lhs, rhs);
+    }
+    if (!key_ok || !range_ok) {
+      K.status[i] = key_ok ? ST_REJECT : ST_BAD_KEY;
+      continue;
+    }
+    fe_canon(qx);  // canonical Montgomery: what a table-free key's entry holds (k_point_entries)
+    fe_canon(qy);
+    uint32_t U1[8], U2[8];
+    load_scalars<LANE_INV>(A, i, U1, U2);
+    bool inf = true;
+    jac j;
+    ladder_mul(j, inf, U2, qx, qy);
+    comb_complete(j, inf, U1, K.tabG, K.wg);
+    verify_finish_jac(A, i, j, inf);
+  }
+}
+
 #ifdef MBFT_CLOCK_STAMP
 // Clock builds only (tools/ab_build_def.sh clk "-DMBFT_CLOCK_STAMP"): per
 // k_verify workgroup, shader cycles (s_memtime) and 100 MHz wall ticks
@@ -3335,7 +3414,7 @@ long split_max_env() {
   return v;
 }
 
-static int device_cus() {
+int device_cus() {
   static const int ncu = [] {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess)
@@ -3428,6 +3507,19 @@ hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const VerifyPlan&
     if (le != hipSuccess) return le;
     return key_account(KeyAccount{b.slot, b.status, n, b.ndev, t.keys, t.nslots, t.uses, t.rejects}, st);
   }
+  return hipGetLastError();
+}
+
+// The inline-key form, as its plan says (verify_plan.h, verify_keys_plan).
+hipError_t verify_keys(const KeysBatch& b, const uint32_t* tabG, int wg, const mbft::KeysPlan& plan, hipStream_t st) {
+  if (b.n <= 0) return hipSuccess;
+  if (plan.blocks <= 0 || (!plan.lane_inv && !b.winv)) return hipErrorInvalidValue;
+  const KeysArgs K{b.e, b.r, b.s, b.xy, plan.lane_inv ? nullptr : b.winv, tabG, wg, b.n, b.status};
+  const dim3 grid((unsigned)plan.blocks), block(256);
+  if (plan.lane_inv)
+    hipLaunchKernelGGL(k_verify_keys<true>, grid, block, 0, st, K);
+  else
+    hipLaunchKernelGGL(k_verify_keys<false>, grid, block, 0, st, K);
   return hipGetLastError();
 }
 

@@ -89,6 +89,25 @@ constexpr VerifyPlan verify_plan(long n, InvSource src, bool has_count, bool has
   return {VerifyForm::kPairsLane, 2 * n, false, false};
 }
 
+// The inline-key form (k_verify_keys, mbft_verify_prehashed_keys*): one item
+// per lane of 256-thread blocks, grid-stride past kKeysBpc blocks per CU -- the
+// kernel's occupancy (2 waves a SIMD), as k_verify_ladder's grid.  s^-1 by the
+// lane up to lane_inv_max items, from the batch's planes above (the rule of
+// verify_inv_source: no host planes, no count on the device).  The host path
+// sizes the planes from `lane_inv`, the launcher takes the rest.
+constexpr long kKeysBpc = 2;
+struct KeysPlan {
+  bool lane_inv;  // k_verify_keys<true>: no planes, no s^-1 kernel in front
+  long threads;   // one per item, whole blocks of 256
+  long blocks;    // the grid: threads / 256, at most kKeysBpc per CU
+};
+constexpr KeysPlan verify_keys_plan(long n, size_t lane_inv_max, long ncu) {
+  const long want = n <= 0 ? 0 : (n + 255) / 256;
+  const long cap = (ncu < 1 ? 1 : ncu) * kKeysBpc;
+  return {verify_inv_source(n, lane_inv_max, false, false) == InvSource::kNone, want * 256,
+          want < cap ? want : cap};
+}
+
 // `slowq`: the exact-path queue (n words), its length, the table-free queue's
 // length (side by side), then (64-word aligned) the table-free queue (n
 // words) and (64-word aligned) kSpillPlanes planes of one word per grid
