@@ -1,12 +1,14 @@
 // Test-only harness (tests/test_gpu_arena_dev.py, tests/test_gpu_msg_dedup.py,
-// tests/test_gpu_msg_number.py): runs the device message layer stage by stage
+// tests/test_gpu_msg_number.py, tests/test_gpu_msg_replay.py): runs the device
+// message layer stage by stage
 // through the library's own launchers (minbft_amd/csrc/msg_dev.h, linked from
 // libminbft_amd.so) over a fabricated MsgDevArgs -- no context -- and hands
 // every intermediate array back, so that Python can check each stage against
 // a model and can INJECT state no honest run produces on demand: candidates
 // with equal content hashes and different content (stage_run's forcing),
 // numbering inputs of any shape (number_run), uploads of any length
-// (upload_run).  arena_run calls the blocked arena reads of arena_dev.h,
+// (upload_run), checks, call outcomes and epoch state of any shape for the
+// optimistic replay (replay_run).  arena_run calls the blocked arena reads of arena_dev.h,
 // included directly, one case per lane.  The functions are the product's own,
 // called, not restated.  Every entry point checks its arguments before the
 // first launch (fields inside the arena, indices in range, table capacity),
@@ -381,6 +383,69 @@ int upload_run(const uint8_t* src, uint64_t bytes, uint64_t fill, uint8_t* out) 
   R.sync();
   if (!R.ok) return -4;
   R.back(out, dst, (size_t)fill + 64);
+  return R.ok ? 0 : -5;
+}
+
+// The optimistic replay alone (mbft_launch::msg_replay: k_replay_caps,
+// k_replay_cap_epoch, k_replay_eval) over injected state: the packed checks
+// of n messages, call_of for their 3n candidate slots, nc unique calls'
+// outcomes (info, status) and the epoch state of G fingerprint groups.
+//   out (out_len >= n + 8 words) and cap (cap_len >= 2G + 1 + 8 words; laid
+//   out as msgdev.cpp lays it out: [0, G) cap_pos, [G, 2G) cap_epoch, [2G]
+//   first_bad) are IN/OUT: uploaded whole as the caller filled them (cap_pos
+//   ~0 and first_bad n, as msgdev.cpp does; sentinels behind), copied back
+//   whole after the launch.
+// Checked before anything is launched: every check count <= 3, every
+// call_of < nc (all 3n: a check's slot comes from its byte, 0..2; slot 3
+// refused; no call check without a call), every USIG call's fpg < G,
+// epoch_set 0 / 1.  *launch_rc = the
+// launcher's own return value (n == 0: success, nothing launched).
+int replay_run(long n, const uint32_t* chk, const uint32_t* call_of, const DevCallInfo* info,
+               const uint8_t* status, uint32_t nc, uint32_t G, const uint8_t* epoch_set,
+               const uint64_t* epoch_val, int32_t* out, uint64_t out_len, uint64_t* cap, uint64_t cap_len,
+               int* launch_rc) {
+  if (n < 0 || n > kMaxMsgs || nc > 3u * (uint32_t)kMaxMsgs || G > (1u << 20) ||
+      out_len < (uint64_t)n + 8 || out_len > (uint64_t)n + 4096 || cap_len < 2ull * G + 1 + 8 ||
+      cap_len > 2ull * G + 1 + 4096)
+    return -1;
+  const size_t nc3 = 3 * (size_t)n;
+  for (long i = 0; i < n; i++) {
+    const uint32_t w = chk[i], nq = w & 0xFFu;
+    if (nq > 3) return -1;
+    for (uint32_t q = 0; q < nq; q++) {
+      const uint32_t b = (w >> (8 + 8 * q)) & 0xFFu;
+      if ((b & 3u) == kChkCall && (nc == 0 || ((b >> 6) & 3u) > 2u)) return -1;
+    }
+  }
+  for (size_t c = 0; c < nc3; c++)
+    if (nc != 0 && call_of[c] >= nc) return -1;
+  for (uint32_t k = 0; k < nc; k++)
+    if (info[k].usig > 1 || (info[k].usig && info[k].fpg >= G)) return -1;
+  for (uint32_t g = 0; g < G; g++)
+    if (epoch_set[g] > 1) return -1;
+  Run R;
+  MsgDevArgs a{};
+  a.n = n;
+  a.chk = R.in(chk, (size_t)n);
+  a.call_of = R.in(call_of, nc3);
+  a.info = R.in(info, nc);
+  a.status = R.in(status, nc);
+  a.epoch_set = R.in(epoch_set, G);
+  a.epoch_val = R.in(epoch_val, G);
+  a.ngroups = G;
+  uint64_t* d_cap = R.in(cap, (size_t)cap_len);
+  a.cap_pos = reinterpret_cast<unsigned long long*>(d_cap);
+  a.cap_epoch = d_cap + G;
+  a.first_bad = reinterpret_cast<unsigned long long*>(d_cap) + 2 * (size_t)G;
+  a.out = R.in(out, (size_t)out_len);
+  if (!R.stream()) return -2;
+  const hipError_t rc = mbft_launch::msg_replay(a, R.st);
+  *launch_rc = (int)rc;
+  R.launched(rc);
+  R.sync();
+  if (!R.ok) return -4;
+  R.back(out, a.out, (size_t)out_len);
+  R.back(cap, d_cap, (size_t)cap_len);
   return R.ok ? 0 : -5;
 }
 

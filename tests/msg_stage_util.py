@@ -1,5 +1,5 @@
-"""Shared by tests/test_gpu_arena_dev.py, tests/test_gpu_msg_dedup.py and
-tests/test_gpu_msg_number.py: the ctypes side of the test-only harness
+"""Shared by tests/test_gpu_arena_dev.py, tests/test_gpu_msg_dedup.py,
+tests/test_gpu_msg_number.py and tests/test_gpu_msg_replay.py: the ctypes side of the test-only harness
 tests/csrc/msg_stage_check.hip, byte arenas built twice (same fields at the
 same offsets, different filler), and a Python model of the device message
 layer's stages written from the rules msg_kernels.hip cites."""
@@ -43,6 +43,7 @@ def load_harness():
     h.stage_run.argtypes = [vp, lg, vp, u64, u32, u32, vp, vp, u32, u32, vp, vp, u32, vp, i] + [vp] * 15
     h.number_run.argtypes = [lg, vp, vp, vp, u32, i, vp, vp, vp, vp, vp]
     h.upload_run.argtypes = [vp, u64, u64, vp]
+    h.replay_run.argtypes = [lg, vp, vp, vp, vp, u32, u32, vp, vp, vp, u64, vp, u64, vp]
     assert h.msg_stage_rec_size() == REC.itemsize
     assert h.msg_stage_cand_size() == CAND.itemsize
     assert h.msg_stage_info_size() == INFO.itemsize
@@ -158,6 +159,36 @@ def stage_run_both(h, recs, a, b, n_replicas, keys, group=None, one=True):
     for k in x:
         assert np.array_equal(x[k], y[k]), "filler changed " + k
     return x
+
+
+REPLAY_PAD = 8                    # sentinel elements behind out and cap
+OUT_MARK, CAP_MARK = 0x5A5A5A5A, 0x5A5A5A5A5A5A5A5A
+NO_CAPTURE = (1 << 64) - 1        # cap_pos of a group nothing captures
+
+
+def replay_run(h, chk, call_of, info, status, epoch_set, epoch_val):
+    """mbft_launch::msg_replay once over injected state.  out and cap go in
+    as msgdev.cpp fills them -- cap = cap_pos[G] (~0) | cap_epoch[G] |
+    first_bad (n) -- with REPLAY_PAD sentinels behind each, and out[:n] and
+    cap_epoch hold the sentinel value too (msgdev.cpp leaves them as they
+    were).  -> the launcher's return value, out and cap whole."""
+    n, nc, G = len(chk), len(info), len(epoch_set)
+    assert len(call_of) == 3 * n and len(status) == nc and len(epoch_val) == G
+    chk = np.ascontiguousarray(chk, dtype=np.uint32)
+    call_of = np.ascontiguousarray(call_of, dtype=np.uint32)
+    info = np.ascontiguousarray(info, dtype=INFO)
+    status = np.ascontiguousarray(status, dtype=np.uint8)
+    epoch_set = np.ascontiguousarray(epoch_set, dtype=np.uint8)
+    epoch_val = np.ascontiguousarray(epoch_val, dtype=np.uint64)
+    out = np.full(n + REPLAY_PAD, OUT_MARK, dtype=np.int32)
+    cap = np.full(2 * G + 1 + REPLAY_PAD, CAP_MARK, dtype=np.uint64)
+    cap[:G] = NO_CAPTURE
+    cap[2 * G] = n
+    rc = np.full(1, -1, dtype=np.int32)
+    r = h.replay_run(n, ptr(chk), ptr(call_of), ptr(info), ptr(status), nc, G, ptr(epoch_set), ptr(epoch_val),
+                     ptr(out), len(out), ptr(cap), len(cap), ptr(rc))
+    assert r == 0, r
+    return int(rc[0]), out, cap
 
 
 # --------------------------------------------------------------------------

@@ -100,6 +100,35 @@ def test_flat_c3_large_vs_oracle_and_host(lib, monkeypatch):
     assert (got_dev2 == want).all()
 
 
+def test_flat_c3_more_than_64_groups(lib, monkeypatch):
+    """f = 40: 81 replicas with distinct USIG keys, so 81 fingerprint groups
+    -- past the 64 of one k_replay_cap_epoch workgroup -- with the faults.
+    The device path, the host path and a second device call on the same
+    context (every epoch captured by then) agree with the oracle: what
+    msgdev.cpp commits of cap_pos / cap_epoch / first_bad and hands to the
+    host tail is the state tests/test_gpu_msg_replay.py checks in the
+    harness."""
+    from oracle import p256 as o
+    _fast_oracle(monkeypatch)
+    rng = random.Random(0xF1A7 + 40)
+    n, msgs, keys = _c3_streams(40, 2, rng, faults=True)
+    assert n == 81 and len(keys[o.ROLE_USIG]) == 81
+    ks = o.KeyStore()
+    ks.keys = {role: dict(m) for role, m in keys.items()}
+    want = np.array(o.validate_messages(o.Authenticator(ks), msgs, n, 0))
+    assert (want == 0).sum() > 64 and (want != 0).any()
+    a = _auth_for(keys, window=8)  # 82 keys: small tables
+    try:
+        got_dev = a.validate_messages_via_flat(msgs, n, 0)
+        got_host = a.validate_messages(msgs, n, 0)
+        got_dev2 = a.validate_messages_via_flat(msgs, n, 0)
+    finally:
+        a.close()
+    assert (got_dev == want).all(), np.nonzero(got_dev != want)[0][:10]
+    assert (got_host == want).all(), np.nonzero(got_host != want)[0][:10]
+    assert (got_dev2 == want).all(), np.nonzero(got_dev2 != want)[0][:10]
+
+
 def _mutate(msgs, rng):
     """Adversarial variants of C3 messages (each on a stream of its own so
     that stream stops do not hide the later ones)."""
