@@ -3482,21 +3482,19 @@ hipError_t verify(const VerifyBatch& b, const VerifyTables& t, const VerifyPlan&
       }
       static const int bpc = (int)env_long("MBFT_VERIFY_BPC", 0);
       const long ncu = device_cus();
-      const long vblocks = bpc > 0 && blocks > bpc * ncu ? bpc * ncu : blocks;
+      const long vblocks = verify_large_blocks(blocks, bpc, ncu);
       A.sstride = (uint32_t)(vblocks * 256);
       // MINW = 3 waves/SIMD (the trace summaries under profiles/ name k_verify<3>)
       hipLaunchKernelGGL((k_verify<3>), dim3((unsigned)vblocks), block, 0, st, A);
       // the queued items: a grid of up to kSlowBpc blocks per CU (one wave per
       // SIMD) that exits at once when the queue is empty; its threads index
-      // the same spill planes (A.sstride)
-      constexpr int kSlowBpc = 4;
-      long sblocks = blocks < ncu * kSlowBpc ? blocks : ncu * kSlowBpc;
-      if (sblocks > vblocks) sblocks = vblocks;
+      // the same spill planes (A.sstride): verify_slow_blocks keeps it inside them
+      const long sblocks = verify_slow_blocks(blocks, vblocks, ncu);
       hipLaunchKernelGGL(k_verify_slow, dim3((unsigned)sblocks), block, 0, st, A);
       // the table-free items: two blocks per CU at the most (the kernel's
       // occupancy), grid-stride over the queue
       if (t.table_free) {
-        const long lblocks = blocks < ncu * 2 ? blocks : ncu * 2;
+        const long lblocks = verify_ladder_blocks(blocks, ncu);
         hipLaunchKernelGGL(k_verify_ladder, dim3((unsigned)lblocks), block, 0, st, A);
       }
       break;

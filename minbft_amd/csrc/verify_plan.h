@@ -89,6 +89,29 @@ constexpr VerifyPlan verify_plan(long n, InvSource src, bool has_count, bool has
   return {VerifyForm::kPairsLane, 2 * n, false, false};
 }
 
+// The kLarge form's three grids (mbft_launch::verify), in blocks of 256; every
+// kernel strides over what its grid does not cover.  `blocks`: the plan's
+// threads in whole blocks, ncu: the device's compute units.
+// k_verify: one item per lane; bpc > 0 (MBFT_VERIFY_BPC) caps the grid at bpc
+// blocks per CU.  Its threads are the spill planes' stride (VerifyArgs.sstride).
+constexpr long verify_large_blocks(long blocks, long bpc, long ncu) {
+  return bpc > 0 && blocks > bpc * ncu ? bpc * ncu : blocks;
+}
+// k_verify_slow: one queued item per lane pair, up to kSlowBpc blocks per CU
+// (one wave per SIMD), never more than k_verify's grid (vblocks): its threads
+// index the same spill planes.
+constexpr long kSlowBpc = 4;
+constexpr long verify_slow_blocks(long blocks, long vblocks, long ncu) {
+  const long s = blocks < ncu * kSlowBpc ? blocks : ncu * kSlowBpc;
+  return s > vblocks ? vblocks : s;
+}
+// k_verify_ladder: one queued item per lane, two blocks per CU at the most
+// (the kernel's occupancy).
+constexpr long kLadderBpc = 2;
+constexpr long verify_ladder_blocks(long blocks, long ncu) {
+  return blocks < ncu * kLadderBpc ? blocks : ncu * kLadderBpc;
+}
+
 // The inline-key form (k_verify_keys, mbft_verify_prehashed_keys*): one item
 // per lane of 256-thread blocks, grid-stride past kKeysBpc blocks per CU -- the
 // kernel's occupancy (2 waves a SIMD), as k_verify_ladder's grid.  s^-1 by the

@@ -190,10 +190,14 @@ def test_batch_sizes_tree_shapes(gpu_auth, n):
 
 def test_exact_path_queue(gpu_auth):
     """Items whose u2 has a zero comb window (crafted with the signer's key:
-    u2 = v 2^W, s = r / u2, e = r (k / u2 - d)) leave the fast loop for the
-    queued exact path (k_verify_slow): 96 of them, valid and with a flipped
-    digest, spread over a 4,096-item batch of ordinary signatures at key
-    window 16 -- a wave holding several, one, or none -- against the C oracle."""
+    u2 = v 2^W, s = r / u2, e = r (k / u2 - d)) stay in the fast loop:
+    comb_step resolves a zero digit there, around the unconditional mixed
+    addition, through the spill planes -- they are NOT queued for the exact
+    path (k_verify_slow), as tests/test_gpu_verify_passes.py reads off the
+    queue itself (test_zero_window_items_stay_on_the_fast_path).  96 of them,
+    valid and with a flipped digest, spread over a 4,096-item batch of ordinary
+    signatures at key window 16 -- a wave holding several, one, or none (the
+    rare-step branch is wave-uniform) -- against the C oracle."""
     import hashlib
     import random
 
@@ -233,10 +237,13 @@ def test_exact_path_queue(gpu_auth):
 
 
 def test_exact_path_queue_many(gpu_auth):
-    """A long exact-path queue: 8,192 crafted items (u2 = v 2^16: a zero
+    """Many zero-digit steps: 8,192 crafted items (u2 = v 2^16: a zero
     first key window at window 16), every third with a flipped digest, at
     every 4th position of a 32,768-item batch, run twice back to back (the
-    queue buffers are reused); every status against the construction."""
+    spill planes are reused); every status against the construction.  Such
+    items do not reach the exact-path queue (comb_step handles a zero digit
+    in the fast path); test_exact_path_queue_degenerate and
+    tests/test_gpu_verify_passes.py fill that queue."""
     import random
 
     import torch

@@ -10,7 +10,11 @@ of the 256-rounded threads the form's kernel indexes: 4 n for the lane
 quads, 2 n for the lane pairs, the grid for k_verify (a MBFT_VERIFY_BPC cap
 only lowers it), none for the split kernel.  The old size, verify_words(n, n
 <= lane_inv_max || count), did not: host planes past MBFT_LANE_INV_MAX got
-n threads of scratch under the lane quads' 4 n (NAMED_ROW)."""
+n threads of scratch under the lane quads' 4 n (NAMED_ROW).
+(c) The large form's three grids -- k_verify under a MBFT_VERIFY_BPC cap,
+k_verify_slow at four blocks per CU clamped to k_verify's, k_verify_ladder at
+two per CU -- are the expressions the launcher held, below, at and above each
+cap on 1, 8, 256 and 304 CUs."""
 import ctypes
 import itertools
 
@@ -113,3 +117,68 @@ def test_old_size_missed_the_named_row(lib):
     need = scratch_offset(n) + 36 * round256(4 * n)
     assert old_words < need
     assert plan(lib, NAMED_ROW)["words"] >= need
+
+
+# ------------------------------------------------- the kLarge form's three grids
+def large_grids(lib, blocks, bpc, ncu):
+    out = (ctypes.c_long * 5)()
+    lib.verify_large_grids_check(blocks, bpc, ncu, out)
+    return tuple(out)
+
+
+def launcher_grids(blocks, bpc, ncu):
+    """mbft_launch::verify's kLarge branch as it stood before the rules moved
+    into verify_plan.h, expression for expression."""
+    vblocks = bpc * ncu if bpc > 0 and blocks > bpc * ncu else blocks
+    k_slow_bpc = 4
+    sblocks = blocks if blocks < ncu * k_slow_bpc else ncu * k_slow_bpc
+    if sblocks > vblocks:
+        sblocks = vblocks
+    lblocks = blocks if blocks < ncu * 2 else ncu * 2
+    return vblocks, sblocks, lblocks
+
+
+NCUS = (1, 8, 256, 304)
+BPCS = (0, 1, 2, 3, 4, 8)
+
+
+def grid_rows():
+    """Below, at and above every cap: bpc ncu (k_verify), 4 ncu (k_verify_slow),
+    2 ncu (k_verify_ladder), for each ncu and bpc; plus one block and 2^22."""
+    rows = []
+    for ncu, bpc in itertools.product(NCUS, BPCS):
+        edges = {1, 1 << 22}
+        for cap in (bpc * ncu, 2 * ncu, 4 * ncu):
+            edges.update(b for b in (cap - 1, cap, cap + 1) if b >= 1)
+        rows += [(b, bpc, ncu) for b in sorted(edges)]
+    return rows
+
+
+def test_large_grids_are_the_launchers(lib):
+    lib.verify_large_grids_check.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p]
+    lib.verify_large_grids_check.restype = None
+    rows = grid_rows()
+    assert len(rows) > 200
+    capped = slow_clamped = 0
+    for blocks, bpc, ncu in rows:
+        got = large_grids(lib, blocks, bpc, ncu)
+        assert got[3:] == (4, 2)
+        assert got[:3] == launcher_grids(blocks, bpc, ncu), (blocks, bpc, ncu)
+        v, s, ld = got[:3]
+        # what the kernels rely on: no empty grid, none past the plan's blocks,
+        # k_verify_slow inside the spill planes laid out for k_verify's threads
+        assert 1 <= s <= v <= blocks and 1 <= ld <= blocks, (blocks, bpc, ncu)
+        assert s <= 4 * ncu and ld <= 2 * ncu and (bpc == 0 or v <= bpc * ncu)
+        capped += v < blocks
+        slow_clamped += s < min(blocks, 4 * ncu)
+    assert capped > 50 and slow_clamped > 20
+    # the sizes the issue of the second pass names, on 256 CUs
+    assert large_grids(lib, 1 << 12, 0, 256)[:3] == (4096, 1024, 512)  # 1M items: 8 ladder passes
+    assert large_grids(lib, 512, 0, 256)[:3] == (512, 512, 512)        # 131,072 items: the last single pass
+    assert large_grids(lib, 513, 0, 256)[:3] == (513, 513, 512)
+    # bpc = 1: the ladder's 2 ncu blocks are MORE than k_verify's grid (it spills
+    # nothing), k_verify_slow's are clamped to it
+    assert large_grids(lib, 2054, 1, 256)[:3] == (256, 256, 512)
+    assert large_grids(lib, 2054, 1, 304)[:3] == (304, 304, 608)
+    assert large_grids(lib, 17, 1, 8)[:3] == (8, 8, 16)
+    assert large_grids(lib, 3, 1, 1)[:3] == (1, 1, 2)
