@@ -656,6 +656,62 @@ int mbft_scheme_verify_flat32(mbft_ctx* ctx, const uint8_t* msgs, const uint32_t
                               const uint8_t* tags, const uint32_t* tag_off, const uint8_t* xy,
                               size_t n, uint8_t* status_out);
 
+/* The P-384 class: the same boundary over secp384r1.  The reference's ECDSA
+ * roles are not tied to one curve -- ecdsaKeySpec.generateKeyPair
+ * (sample/authentication/keymanager.go:368-382) makes P-384 keys at security
+ * parameter 384, parsePublicKey (:352-366, x509.ParsePKIXPublicKey) accepts
+ * them and EcdsaSigCipher.Verify (crypto.go:79-89) calls the curve-generic
+ * ecdsa.Verify.  Keys are given with the call, as in the inline-key class;
+ * P-384 keys cannot be registered (mbft_set_public_key_pkix refuses them).
+ *
+ * mbft_verify_prehashed_p384_keys / _device: e, r, s are n x 48 bytes
+ * big-endian (e = hashToInt(hash) for a 384-bit order: the left-most 48 bytes
+ * of the digest, a shorter digest right-aligned; any value below 2^384, e >= N
+ * included), xy is n x 96 bytes X || Y.  Statuses and their precedence are the
+ * inline-key class's: MBFT_BAD_KEY for X >= p, Y >= p or a point off the curve
+ * ((0, 0) among them), also where r or s is out of range; MBFT_REJECT_SIG for
+ * a valid point with r or s outside [1, N), for a sum at infinity or an x
+ * mismatch; else MBFT_ACCEPT.  One kernel, k_verify_p384: the lane validates
+ * its key, inverts s and runs complete addition formulas -- every degenerate
+ * case (Q = +-G, u1 G = +-u2 Q, u1 = 0) is exact.
+ *
+ * mbft_scheme_verify_p384_flat32: VerifyAuthenticationTag(m, sig, pk) of the
+ * ECDSA roles (crypto.go:120-126 -> 79-89) as mbft_scheme_verify_flat32, xy
+ * 96 bytes a call.  md = m || SHA256("") (crypto.go:121), L = len(m) + 32
+ * bytes: e = md[0:48] for L >= 48; for messages under 16 bytes e is the whole
+ * of md as a big-endian integer, right-aligned in 48 bytes (hashToInt does not
+ * shift: the order's bit length is a byte multiple).  The tag by
+ * mbft_der_parse_sig48's rules: a parse error is MBFT_MALFORMED_DER and wins
+ * over MBFT_BAD_KEY, bytes after the SEQUENCE are ignored.
+ *
+ * mbft_der_parse_sig48: mbft_der_parse_sig at width 48 -- the same grammar,
+ * the same `consumed`; a value outside (0, 2^384) goes on as zero.
+ *
+ * mbft_pkix_parse_p384: parsePublicKey for a P-384 key.  Accepts exactly the
+ * 120-byte SubjectPublicKeyInfo of an uncompressed point (30 76 30 10 06 07 2a
+ * 86 48 ce 3d 02 01 06 05 2b 81 04 00 22 03 62 00 04 || X || Y), validates the
+ * point on the host as x509.ParsePKIXPublicKey does and writes X || Y to xy96.
+ * MBFT_OK, or MBFT_ERR_KEY with mbft_set_public_key_pkix's messages on ctx
+ * (ctx may be NULL: no message is kept).  Takes no lock, touches no GPU.
+ *
+ * Argument rules, locking and statelessness are the inline-key class's: n == 0
+ * returns MBFT_OK, a NULL buffer with n > 0 is MBFT_ERR_ARG; the calls
+ * serialise on the context, work on one with no key and no generator table,
+ * and leave slots, key memory, use counts and the verified-call memo as they
+ * were.  The _device form is asynchronous on hip_stream (NULL: the
+ * context's); d_e, d_r, d_s and d_xy must be 16-byte aligned. */
+int mbft_verify_prehashed_p384_keys(mbft_ctx* ctx, const uint8_t* e, const uint8_t* r, const uint8_t* s,
+                                    const uint8_t* xy, size_t n, uint8_t* status);
+int mbft_verify_prehashed_p384_keys_device(mbft_ctx* ctx, const uint8_t* d_e, const uint8_t* d_r,
+                                           const uint8_t* d_s, const uint8_t* d_xy, size_t n,
+                                           uint8_t* d_status, void* hip_stream);
+int mbft_scheme_verify_p384_flat32(mbft_ctx* ctx, const uint8_t* msgs, const uint32_t* msg_off,
+                                   const uint8_t* tags, const uint32_t* tag_off, const uint8_t* xy,
+                                   size_t n, uint8_t* status_out);
+int mbft_der_parse_sig48(const uint8_t* sig, size_t len, uint8_t r48[48], uint8_t s48[48],
+                         size_t* consumed);
+int mbft_pkix_parse_p384(mbft_ctx* ctx, const uint8_t* pkix, size_t len, uint8_t xy96[96]);
+
 /* Bulk ECDSA signing over decoded digests, for synthetic load generation
  * and tests (the signature format of crypto.go:63-76).  priv32: nkeys x 32 B
  * big-endian scalars; key_idx: n indices (NULL = key 0); e: n x 32 B; r, s:

@@ -104,6 +104,8 @@ EXPORTED = [
     "mbft_rebalance_keys", "mbft_cold_keys",
     "mbft_set_verified_memo", "mbft_get_verified_memo", "mbft_verified_memo_stats", "mbft_clear_verified_memo",
     "mbft_verify_prehashed_keys", "mbft_verify_prehashed_keys_device", "mbft_scheme_verify_flat32",
+    "mbft_verify_prehashed_p384_keys", "mbft_verify_prehashed_p384_keys_device", "mbft_scheme_verify_p384_flat32",
+    "mbft_der_parse_sig48", "mbft_pkix_parse_p384",
 ]
 # (mbft_key_class_cost, the one declaration that returns uint32_t, is typed in load() but not listed: the
 # header check of tests/test_abi.py reads the int / void / uint64_t / size_t / const char* declarations)
@@ -342,6 +344,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "mbft_verify_prehashed_keys": (i, [vp, u8p, u8p, u8p, u8p, sz, vp]),
         "mbft_verify_prehashed_keys_device": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "mbft_scheme_verify_flat32": (i, [vp, vp, vp, vp, vp, vp, sz, vp]),
+        "mbft_verify_prehashed_p384_keys": (i, [vp, u8p, u8p, u8p, u8p, sz, vp]),
+        "mbft_verify_prehashed_p384_keys_device": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
+        "mbft_scheme_verify_p384_flat32": (i, [vp, vp, vp, vp, vp, vp, sz, vp]),
+        "mbft_der_parse_sig48": (i, [u8p, sz, vp, vp, ctypes.POINTER(sz)]),
+        "mbft_pkix_parse_p384": (i, [vp, u8p, sz, vp]),
         "mbft_sign_prehashed": (i, [vp, u8p, sz, vp, u8p, sz, vp, vp]),
         "mbft_sign_prehashed_device": (i, [vp, vp, vp, vp, sz, vp, vp, vp]),
         "mbft_sign_nonce_device": (i, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),

@@ -762,6 +762,52 @@ class Authenticator:
                                                        _buf(xy), n, _buf(out)), "scheme_verify")
         return out
 
+    # The P-384 class (include/minbft_gpu.h): the same
+    # boundary over secp384r1, 48-byte e, r, s and 96-byte keys.
+    def verify_prehashed_p384_keys(self, e: np.ndarray, r: np.ndarray, s: np.ndarray,
+                                   xy: np.ndarray) -> np.ndarray:
+        """mbft_verify_prehashed_p384_keys: e, r, s n x 48 bytes, xy n x 96
+        bytes, big-endian X || Y, item i's own key."""
+        e = np.ascontiguousarray(e, dtype=np.uint8).reshape(-1, 48)
+        r = np.ascontiguousarray(r, dtype=np.uint8).reshape(-1, 48)
+        s = np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 48)
+        xy = np.ascontiguousarray(xy, dtype=np.uint8).reshape(-1, 96)
+        n = e.shape[0]
+        assert r.shape[0] == n and s.shape[0] == n and xy.shape[0] == n
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.mbft_verify_prehashed_p384_keys(self.ctx, _buf(e), _buf(r), _buf(s), _buf(xy),
+                                                             n, _buf(out)), "verify_prehashed_p384_keys")
+        return out
+
+    def verify_prehashed_p384_keys_device(self, d_e: int, d_r: int, d_s: int, d_xy: int, n: int,
+                                          d_status: int, stream: int = 0) -> None:
+        self._check(self.lib.mbft_verify_prehashed_p384_keys_device(
+            self.ctx, ctypes.c_void_p(d_e), ctypes.c_void_p(d_r), ctypes.c_void_p(d_s),
+            ctypes.c_void_p(d_xy), n, ctypes.c_void_p(d_status), ctypes.c_void_p(stream)),
+            "verify_prehashed_p384_keys_device")
+
+    def scheme_verify_p384(self, items) -> np.ndarray:
+        """mbft_scheme_verify_p384_flat32 over calls (msg, tag, xy96)."""
+        n = len(items)
+        out = np.zeros(n, dtype=np.uint8)
+        if n == 0:
+            self._check(self.lib.mbft_scheme_verify_p384_flat32(self.ctx, None, None, None, None, None, 0,
+                                                                _buf(out)), "scheme_verify_p384")
+            return out
+        _, _, mb, mo, tb, to = flat_calls([(0, 0, m, t) for (m, t, _) in items], compact=True)
+        xy = np.frombuffer(b"".join(bytes(q) for (_, _, q) in items), dtype=np.uint8).reshape(n, 96)
+        self._check(self.lib.mbft_scheme_verify_p384_flat32(self.ctx, _buf(mb), _buf(mo), _buf(tb), _buf(to),
+                                                            _buf(xy), n, _buf(out)), "scheme_verify_p384")
+        return out
+
+    def pkix_parse_p384(self, pkix: bytes) -> bytes:
+        """mbft_pkix_parse_p384: the 96 bytes X || Y of a P-384 SPKI; raises
+        on anything else, with the message of set_public_key."""
+        out = np.zeros(96, dtype=np.uint8)
+        der = np.frombuffer(bytes(pkix) or b"\0", dtype=np.uint8)
+        self._check(self.lib.mbft_pkix_parse_p384(self.ctx, _buf(der), len(pkix), _buf(out)), "pkix_parse_p384")
+        return out.tobytes()
+
     def sign_prehashed(self, priv: np.ndarray, e: np.ndarray,
                        key_idx: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         priv = np.ascontiguousarray(priv, dtype=np.uint8).reshape(-1, 32)

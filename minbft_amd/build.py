@@ -26,14 +26,15 @@ ARCH = os.environ.get("MBFT_OFFLOAD_ARCH", "gfx950")
 # signer's kernels with the same ones)
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I", os.path.join(ROOT, "include")]
 
-DEVICE_SOURCES = ["kernels.hip", "msg_kernels.hip", "sign_kernels.hip", "key_account.hip", "key_rank.hip", "memo.hip"]
+DEVICE_SOURCES = ["kernels.hip", "msg_kernels.hip", "sign_kernels.hip", "key_account.hip", "key_rank.hip", "memo.hip",
+                  "p384_kernels.hip"]
 HOST_SOURCES = ["host.cpp", "der.cpp", "messages.cpp", "batch.cpp", "msgdev.cpp", "winv_host.cpp",
-                "sha256_host.cpp", "resident.cpp", "join_host.cpp", "sign.cpp", "keys.cpp"]
+                "sha256_host.cpp", "resident.cpp", "join_host.cpp", "sign.cpp", "keys.cpp", "p384.cpp"]
 HEADERS = ["fe29.h", "ecc.h", "modinv.h", "der_dev.h", "sha256.h", "sha256_dev.h", "authen_dev.h", "arena_dev.h",
            "kernels.h", "verify_plan.h", "key_plan.h", "memo_plan.h", "scalar_dev.h", "env.h",
            "msg_dev.h", "host_internal.h", "join_core.inc",
            "sign_dev.h", "der_enc_dev.h", "sign_kernels.h", "sign_rs_dev.h", "ladder_dev.h",
-           "teeth_dev.h"]
+           "teeth_dev.h", "p384_fe.h", "p384_ecc.h"]
 
 
 def _hipcc() -> str:

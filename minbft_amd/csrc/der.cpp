@@ -60,9 +60,11 @@ bool parse_tag_len(const uint8_t* b, size_t n, size_t& off, TL& t) {
   return true;
 }
 
-// INTEGER contents -> 32-byte big-endian if 0 < v < 2^256, else zeros.
-bool parse_int(const uint8_t* v, size_t len, uint8_t out[32]) {
-  memset(out, 0, 32);
+// INTEGER contents -> W-byte big-endian if 0 < v < 2^(8 W), else zeros
+// (W = 32: P-256; W = 48: P-384, mbft_der_parse_sig48).
+template <size_t W>
+bool parse_int(const uint8_t* v, size_t len, uint8_t out[W]) {
+  memset(out, 0, W);
   if (len == 0) return false;  // empty integer
   if (len > 1 && ((v[0] == 0 && (v[1] & 0x80) == 0) || (v[0] == 0xff && (v[1] & 0x80) == 0x80)))
     return false;  // not minimally encoded
@@ -70,29 +72,28 @@ bool parse_int(const uint8_t* v, size_t len, uint8_t out[32]) {
   size_t i = 0;
   while (i < len && v[i] == 0) i++;
   const size_t mag = len - i;
-  if (mag > 32) return true;  // >= 2^256 >= N: Verify rejects
-  memcpy(out + 32 - mag, v + i, mag);
+  if (mag > W) return true;  // >= 2^(8 W) >= N: Verify rejects
+  memcpy(out + W - mag, v + i, mag);
   return true;
 }
 
-bool parse_int_field(const uint8_t* inner, size_t n, size_t& off, uint8_t out[32]) {
+template <size_t W>
+bool parse_int_field(const uint8_t* inner, size_t n, size_t& off, uint8_t out[W]) {
   if (off == n) return false;  // sequence truncated
   TL t;
   if (!parse_tag_len(inner, n, off, t)) return false;
   if (t.cls != 0 || t.tag != 2 || t.compound) return false;  // tags don't match
   if (t.length > n - off) return false;                       // data truncated
-  const bool ok = parse_int(inner + off, (size_t)t.length, out);
+  const bool ok = parse_int<W>(inner + off, (size_t)t.length, out);
   off += (size_t)t.length;
   return ok;
 }
 
-}  // namespace
-
-extern "C" int mbft_der_parse_sig(const uint8_t* sig, size_t len, uint8_t r32[32],
-                                  uint8_t s32[32], size_t* consumed) {
-  uint8_t r[32], s[32];
-  memset(r32, 0, 32);
-  memset(s32, 0, 32);
+template <size_t W>
+int parse_sig(const uint8_t* sig, size_t len, uint8_t* r_out, uint8_t* s_out, size_t* consumed) {
+  uint8_t r[W], s[W];
+  memset(r_out, 0, W);
+  memset(s_out, 0, W);
   if (len == 0 || sig == nullptr) return 0;  // sequence truncated
   size_t off = 0;
   TL t;
@@ -102,10 +103,23 @@ extern "C" int mbft_der_parse_sig(const uint8_t* sig, size_t len, uint8_t r32[32
   const uint8_t* inner = sig + off;
   const size_t n = (size_t)t.length;
   size_t ioff = 0;
-  if (!parse_int_field(inner, n, ioff, r)) return 0;
-  if (!parse_int_field(inner, n, ioff, s)) return 0;
-  memcpy(r32, r, 32);
-  memcpy(s32, s, 32);
+  if (!parse_int_field<W>(inner, n, ioff, r)) return 0;
+  if (!parse_int_field<W>(inner, n, ioff, s)) return 0;
+  memcpy(r_out, r, W);
+  memcpy(s_out, s, W);
   if (consumed) *consumed = off + n;
   return 1;
+}
+
+}  // namespace
+
+extern "C" int mbft_der_parse_sig(const uint8_t* sig, size_t len, uint8_t r32[32],
+                                  uint8_t s32[32], size_t* consumed) {
+  return parse_sig<32>(sig, len, r32, s32, consumed);
+}
+
+// The same rules at width 48 (P-384).
+extern "C" int mbft_der_parse_sig48(const uint8_t* sig, size_t len, uint8_t r48[48],
+                                    uint8_t s48[48], size_t* consumed) {
+  return parse_sig<48>(sig, len, r48, s48, consumed);
 }

@@ -390,6 +390,15 @@ struct KeysBatch {
 // the device's compute units (what verify_keys_plan and the capped grids take)
 int device_cus();
 hipError_t verify_keys(const KeysBatch& b, const uint32_t* tabG, int wg, const mbft::KeysPlan& plan, hipStream_t st);
+// The P-384 class (k_verify_p384, p384_kernels.hip): n items
+// under keys that stand beside them, e, r, s n x 48 B and xy n x 96 B
+// big-endian, all 16-byte aligned.  Reads nothing of any context.
+struct P384Batch {
+  const uint8_t *e, *r, *s, *xy;
+  long n;
+  uint8_t* status;
+};
+hipError_t verify_p384(const P384Batch& b, const mbft::P384Plan& plan, hipStream_t st);
 // The resident verifier: one 256-thread workgroup per mailbox slot, or two
 // (`two`: one per scalar, each on its own CU).
 hipError_t verify_server(const mbft::ServerArgs& a, int servers, bool two, hipStream_t st);

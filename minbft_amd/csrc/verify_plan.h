@@ -131,6 +131,22 @@ constexpr KeysPlan verify_keys_plan(long n, size_t lane_inv_max, long ncu) {
           want < cap ? want : cap};
 }
 
+// The P-384 class (k_verify_p384, mbft_verify_prehashed_p384_keys*; DESIGN.md
+// §4.14): one item per lane of 256-thread blocks, grid-stride past kP384Bpc
+// blocks per CU -- the kernel's occupancy (one wave a SIMD: the lane's three
+// table points, the accumulator and a product's columns take more than half
+// the register file).  s^-1 is always the lane's own.
+constexpr long kP384Bpc = 1;
+struct P384Plan {
+  long threads;  // one per item, whole blocks of 256
+  long blocks;   // the grid: threads / 256, at most kP384Bpc per CU
+};
+constexpr P384Plan verify_p384_plan(long n, long ncu) {
+  const long want = n <= 0 ? 0 : (n + 255) / 256;
+  const long cap = (ncu < 1 ? 1 : ncu) * kP384Bpc;
+  return {want * 256, want < cap ? want : cap};
+}
+
 // `slowq`: the exact-path queue (n words), its length, the table-free queue's
 // length (side by side), then (64-word aligned) the table-free queue (n
 // words) and (64-word aligned) kSpillPlanes planes of one word per grid
