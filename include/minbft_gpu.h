@@ -552,7 +552,7 @@ int mbft_verify_batch_flat32(mbft_ctx* ctx, const uint8_t* roles, const uint32_t
  * tag_off, and the used ranges of msgs and tags) lies in such allocations,
  * the calls travel to the GPU raw, chunk by chunk, and are decoded there
  * (role / key dispatch, Go-exact DER, the Sum(m) digest, the USIG UI / cert
- * split and digest chain; kernels.hip k_prepare): the host reads none of
+ * split and digest chain; prep_kernels.hip k_prepare): the host reads none of
  * their bytes except the roles (a scan for USIG calls, whose epoch step
  * stays on the host in call order).  Results are identical to the host
  * decode.  A status_out in such memory also receives the statuses straight

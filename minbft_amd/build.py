@@ -1,8 +1,9 @@
 """Build the in-tree HIP library ``minbft_amd/libminbft_amd.so`` for gfx950.
 
-Plain ``hipcc`` invocations (no cmake): the kernels TU is compiled for
-``--offload-arch=gfx950`` only, the host TUs are ordinary C++ linked into the
-same shared object.  Rebuilds only when a source is newer than the library.
+Plain ``hipcc`` invocations (no cmake): the kernel units (``*.hip``) are
+compiled for ``--offload-arch=gfx950`` only, the host units are ordinary C++
+linked into the same shared object.  Rebuilds only when a source is newer than
+the library.
 
     python -m minbft_amd.build [--force]
 """
@@ -26,15 +27,12 @@ ARCH = os.environ.get("MBFT_OFFLOAD_ARCH", "gfx950")
 # signer's kernels with the same ones)
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I", os.path.join(ROOT, "include")]
 
-DEVICE_SOURCES = ["kernels.hip", "msg_kernels.hip", "sign_kernels.hip", "key_account.hip", "key_rank.hip", "memo.hip",
-                  "p384_kernels.hip"]
+# heaviest first (each verify form takes minutes): the pool starts them first
+DEVICE_SOURCES = ["verify_split.hip", "verify_quads.hip", "verify_server.hip", "verify_pairs.hip", "verify_large.hip",
+                  "msg_kernels.hip", "sign_kernels.hip", "prep_kernels.hip", "ninv_kernels.hip", "table_kernels.hip",
+                  "p384_kernels.hip", "key_rank.hip", "memo.hip", "key_account.hip"]
 HOST_SOURCES = ["host.cpp", "der.cpp", "messages.cpp", "batch.cpp", "msgdev.cpp", "winv_host.cpp",
                 "sha256_host.cpp", "resident.cpp", "join_host.cpp", "sign.cpp", "keys.cpp", "p384.cpp"]
-HEADERS = ["fe29.h", "ecc.h", "modinv.h", "der_dev.h", "sha256.h", "sha256_dev.h", "authen_dev.h", "arena_dev.h",
-           "kernels.h", "verify_plan.h", "key_plan.h", "memo_plan.h", "scalar_dev.h", "env.h",
-           "msg_dev.h", "host_internal.h", "join_core.inc",
-           "sign_dev.h", "der_enc_dev.h", "sign_kernels.h", "sign_rs_dev.h", "ladder_dev.h",
-           "teeth_dev.h", "p384_fe.h", "p384_ecc.h"]
 
 
 def _hipcc() -> str:
@@ -42,13 +40,6 @@ def _hipcc() -> str:
         if c and os.path.exists(c):
             return c
     raise RuntimeError("hipcc not found (ROCm required to build minbft_amd)")
-
-
-def _inputs():
-    files = [os.path.join(CSRC, f) for f in DEVICE_SOURCES + HOST_SOURCES + HEADERS]
-    files.append(os.path.join(ROOT, "include", "minbft_gpu.h"))
-    files.append(os.path.abspath(__file__))
-    return files
 
 
 def _deps(src: str) -> list:
@@ -65,6 +56,11 @@ def _deps(src: str) -> list:
             for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', fh.read(), re.M):
                 todo.append(os.path.normpath(os.path.join(os.path.dirname(f), inc)))
     return sorted(seen) + [os.path.join(ROOT, "include", "minbft_gpu.h"), os.path.abspath(__file__)]
+
+
+def _inputs() -> set:
+    """Every file the library is built from: _deps() of every source."""
+    return {d for f in DEVICE_SOURCES + HOST_SOURCES for d in _deps(os.path.join(CSRC, f))}
 
 
 def up_to_date() -> bool:
@@ -101,7 +97,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     stale = [j for j in jobs if force or not os.path.exists(j[1])
              or os.path.getmtime(j[1]) < max(os.path.getmtime(d) for d in _deps(j[0][-3]))]
     if stale:
-        with ThreadPoolExecutor(max_workers=len(stale)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(stale), int(os.environ.get("MAX_JOBS", 16)))) as ex:
             list(ex.map(lambda j: run(j[0]), stale))
     tmp = LIB + ".tmp"
     run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", tmp, *[o for _, o in jobs]])

@@ -5,7 +5,7 @@
 // (usig/sgx/sgx-usig.go:99-101, usig-enclave.go:204-214,
 // e = SHA256(SHA256(AuthenBytes) || epoch_le || counter_le)).  One call per
 // lane; the message bytes sit in big-endian words w[], placed at
-// compile-time offsets.  Used by k_authen_e (kernels.hip) and the device
+// compile-time offsets.  Used by k_authen_e (prep_kernels.hip) and the device
 // message layer (msg_kernels.hip).
 #pragma once
 #include "kernels.h"

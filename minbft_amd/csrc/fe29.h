@@ -578,7 +578,7 @@ MBFT_DEV void fn_from_mont(fe& o, const fe& a) {
 }
 
 // a^(N-2) mod N, Montgomery in/out (per-lane Fermat; the batched path in
-// kernels.hip amortizes this across many signatures).
+// ninv_kernels.hip amortizes this across many signatures).
 MBFT_DEV void fn_inv(fe& o, const fe& a) {
   fe r = a;
 #pragma unroll 1

@@ -1,4 +1,5 @@
-// Host-side launch wrappers for the kernels in kernels.hip.
+// Host-side launch wrappers for the kernels of every .hip unit: the one header
+// the host units include.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,6 +1,6 @@
 // Per-key use counts (mbft_set_key_accounting): the stage that ends a verify
 // batch while accounting is on.  A translation unit of its own: the verify
-// kernels of kernels.hip are compiled exactly as without it.
+// kernels (verify_*.hip) are compiled exactly as without it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -2,8 +2,8 @@
 // mbft_age_key_usage): the use counts are aged, binned and
 // turned into lists of slots where they are, on the GPU -- the host sees a
 // histogram and the slots that move, never the per-slot counters.  A
-// translation unit of its own, as key_account.hip: the verify kernels of
-// kernels.hip are compiled exactly as without it.
+// translation unit of its own, as key_account.hip: the verify kernels
+// (verify_*.hip) are compiled exactly as without it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

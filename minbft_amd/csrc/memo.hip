@@ -1,6 +1,6 @@
 // The verified-call memo's two stages (mbft_set_verified_memo; memo_plan.h,
 // DESIGN.md §4.12): k_memo_probe in front of a pass's verify, k_memo_commit
-// behind it.  A translation unit of its own: the verify kernels of kernels.hip
+// behind it.  A translation unit of its own: the verify kernels (verify_*.hip)
 // are compiled exactly as without it.
 //
 // Passes on different lanes of one device share one table, so a commit may run

@@ -1,6 +1,6 @@
 // Variable-time modular inversion mod N (the P-256 group order) by
 // Bernstein-Yang divsteps ("safegcd"), for the ONE value at the root of the
-// batched s^-1 tree (kernels.hip k_ninv_top).  Verification inputs are
+// batched s^-1 tree (ninv_kernels.hip k_ninv_top).  Verification inputs are
 // public, so variable time is fine.  One lane runs it: where Fermat
 // (x^(N-2): 255 squarings + ~40 multiplies, ~60K dependent VALU ops) leaves
 // a single wave latency-bound for ~0.15 ms, divsteps need ~20 batches of 30

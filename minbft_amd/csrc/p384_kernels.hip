@@ -1,6 +1,6 @@
 // The P-384 class (mbft_verify_prehashed_p384_keys*): ECDSA
 // over secp384r1 under keys that stand beside the items.  A translation unit
-// of its own: nothing here is shared with kernels.hip but the launch plan.
+// of its own: nothing here is shared with the P-256 kernel units but the launch plan.
 //
 //   k_verify_p384   one item per lane, 256-thread blocks, grid-stride: the
 //                   lane validates its key, inverts s itself, runs the joint

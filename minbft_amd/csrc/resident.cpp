@@ -1,5 +1,5 @@
 // The resident single-call verifier, host side (mbft_set_resident; the kernel
-// is kernels.hip k_verify_server).  VerifyMessageAuthenTag one call at a time
+// is verify_server.hip k_verify_server).  VerifyMessageAuthenTag one call at a time
 // (api/api.go:133-144, sample/authentication/authenticator.go:121-134) costs
 // a kernel launch, a stream's worth of HIP API time and, under concurrency, a
 // wait for the batch in flight (the coalescer, batch.cpp).  Here a kernel

@@ -1,4 +1,4 @@
-// The verifier's scalar side, device code shared by kernels.hip and the
+// The verifier's scalar side, device code shared by the verifier's kernel units and the
 // test-only harness tests/csrc/field_check.hip: the window shift and signed
 // recoding of the comb (shr_words, comb_digit), u1 = e / s and u2 = r / s
 // from the s^-1 planes (scalars), the whole-wave inversion mod N
@@ -20,7 +20,7 @@ MBFT_DEV void shr_words(uint32_t (&U)[8], int W) {
   U[7] >>= W;
 }
 
-// Signed recoding of the current window (layout: kernels.hip, k_table_fill): `u` =
+// Signed recoding of the current window (layout: table_kernels.hip, k_table_fill): `u` =
 // the scalar's low word after the previous shifts, `carry` in/out.  Returns
 // the table index of |d| (0 for d == 0, an entry that exists; `zero` flags
 // the digit), `neg` = d < 0.

@@ -4,7 +4,7 @@
 //  * the RFC 6979 nonce with HMAC-SHA-256 (Rfc6979, rfc6979_next) exactly as
 //    oracle/p256.py rfc6979_k states it, so a tag is reproducible from (d, e);
 //  * the signed window recoding of the nonce (sign_digit) -- the digits of
-//    the comb layout in kernels.hip (k_table_fill) -- and
+//    the comb layout in table_kernels.hip (k_table_fill) -- and
 //  * the masked pick of a lane's table entry out of a whole window read at
 //    wave-uniform addresses (sign_pick);
 //  * the byte format of a software-USIG UI (usig_ui_write; k_usig_uis,
@@ -15,7 +15,7 @@
 //
 // 256-bit values are 8 big-endian-numeric words (b[0] = bytes 0..3 of the 32
 // big-endian bytes) on the hash side and 8 little-endian words on the
-// recoding side, as in kernels.hip.
+// recoding side, as in the verifier (words_dev.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -165,7 +165,7 @@ MBFT_HD bool rfc6979_next(Rfc6979& g, const uint32_t q[8], uint32_t k[8], int& l
 }
 
 // ---------------------------------------------------------------------------
-// Window recoding, low window first (the signed-digit comb of kernels.hip):
+// Window recoding, low window first (the signed-digit comb of scalar_dev.h):
 // U = the scalar's 8 little-endian words, shifted right by W after each digit.
 // x = low W bits + carry; x > 2^(W-1) -> digit x - 2^W, carry 1; the last
 // window (top) keeps x: 0 <= digit <= 2^(256 - (S-1) W).  Returns |digit|;

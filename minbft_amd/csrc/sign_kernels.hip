@@ -1,7 +1,7 @@
 // k_sign_tags: the batch GenerateMessageAuthenTag of the ECDSA roles
 // (sample/authentication/crypto.go:57-76 ecdsaSigCipher.Sign, reached from
 // authenticator.go GenerateMessageAuthenTag; api/api.go:133-144), one tag per
-// lane, fit for a key that protects something -- unlike k_sign (kernels.hip),
+// lane, fit for a key that protects something -- unlike k_sign (prep_kernels.hip),
 // whose comb gathers table entries at nonce-dependent addresses.
 //
 // Per lane, from the digest input e and the role's private key d:

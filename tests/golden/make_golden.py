@@ -110,7 +110,7 @@ def signed_instance(d, e_int):
 
 def signed_digits(u, W):
     """The GPU comb's signed-digit recoding of a scalar u < 2^256 (W-bit
-    windows, low to high; minbft_amd/csrc/kernels.hip comb_digit): x = window
+    windows, low to high; minbft_amd/csrc/scalar_dev.h comb_digit): x = window
     bits + carry, x > 2^(W-1) -> digit x - 2^W and carry 1; the last window
     takes its bits + carry unrecoded.  sum(d_i 2^(W i)) == u."""
     S = -(-256 // W)
@@ -342,7 +342,7 @@ SMALL_WINDOWS = (4, 5, 6, 7)
 
 def small_window_seams(W):
     """The window indices at which some verify form starts a range of a
-    W-bit comb or leaves the LDS preload (kernels.hip: kSplitPre = 16 windows
+    W-bit comb or leaves the LDS preload (split_dev.h: kSplitPre = 16 windows
     from a range's start): the split and resident one-workgroup forms and the
     quads' lanes split at mid, the resident two-workgroup form at j S / 4,
     the pairs' and quads' generator lanes start at window 2 after the

@@ -10,7 +10,7 @@ kernel.
   signer through every entry form: single calls, the host decode, the GPU
   decode (device (role, id) -> slot map rebuilt), the two-phase form and the
   device message layer -- and still reject ids that are still missing.
-* k_verify_pairs' wave-uniform branch (kernels.hip verify_pair): a wave
+* k_verify_pairs' wave-uniform branch (pair_dev.h verify_pair): a wave
   holding ONE live item inverts s with all 64 lanes (modinv_n_var_wave).
   Every golden prehashed vector is placed as the only live item of its wave
   among dead items (unknown key slot, r = 0, s = N, s = 0), at lanes other than

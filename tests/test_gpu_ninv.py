@@ -4,7 +4,7 @@ batch_inverse_s_pipelined through the test-only harness
 tests/csrc/launch_check.hip) against big integers.
 
 The verifier multiplies e and r by these planes and then makes u1, u2
-canonical with ONE conditional subtraction (kernels.hip scalars()), which
+canonical with ONE conditional subtraction (scalar_dev.h scalars()), which
 rests on every plane value w being below 2^258 with normalized limbs.  The
 suite otherwise sees the planes only through accept / reject of signatures
 with random s; here, for every item of batches at each form's chain and

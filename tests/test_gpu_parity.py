@@ -6,7 +6,7 @@ windows at run time, so every window size the library accepts is one code
 path; these tests cover the key windows 8/16 on the full golden set, each
 large generator window (20..29) on the full set, and each large key window
 with its own accumulator-collision vectors (tests/golden/comb_windows.json),
-all in the signed-digit layout (kernels.hip comb_digit).
+all in the signed-digit layout (scalar_dev.h comb_digit).
 """
 import numpy as np
 import pytest

@@ -1,5 +1,5 @@
 """The resident single-call verifier (mbft_set_resident; resident.cpp,
-kernels.hip k_verify_server) against the oracle and the golden vectors:
+verify_server.hip k_verify_server) against the oracle and the golden vectors:
 VerifyMessageAuthenTag (sample/authentication/authenticator.go:121-134)
 one call at a time and from many threads at once, through a kernel that
 stays on the GPU between calls -- the same statuses as every other path,

@@ -1,4 +1,4 @@
-"""The argument behind k_verify_quads' joins (kernels.hip verify_quad): the
+"""The argument behind k_verify_quads' joins (verify_quads.hip verify_quad): the
 low and high halves of one scalar's signed-digit comb windows never meet in
 a degenerate addition.  With u = a + b (a: windows [0, mid), b: [mid, S)),
 a == -b (mod N) only for u == 0, and a == b (mod N) needs u = 2 a + N with a
@@ -12,7 +12,7 @@ N = 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551
 
 
 def split(u, W):
-    """(a, b): the comb recoding of u (kernels.hip comb_digit, top window
+    """(a, b): the comb recoding of u (scalar_dev.h comb_digit, top window
     unsigned) summed over the low and the high half of its windows."""
     S = (256 + W - 1) // W
     mid = (S + 1) // 2

@@ -1,6 +1,6 @@
 """Instruction histogram of the loops of one kernel in a gfx950 .s dump.
 
-    hipcc -x hip --offload-arch=gfx950 --cuda-device-only -O3 -S kernels.hip -o k.s
+    hipcc -x hip --offload-arch=gfx950 --cuda-device-only -O3 -S verify_large.hip -o k.s
     python tools/isa_hist.py k.s _Z8k_verifyILi3EEv10VerifyArgs
 
 For every backward branch (a loop) prints the body's instruction count by

@@ -1,6 +1,6 @@
 """Where a k_verify comb step's cycles go: stamps in a
 timing build of the library (bash tools/ab_build_def.sh stp
-"-DMBFT_STEP_TIMING"; kernels.hip comb_step), per wave and step: waiting for
+"-DMBFT_STEP_TIMING"; verify_dev.h comb_step), per wave and step: waiting for
 the gather prefetched one step earlier, reading it from LDS, issuing the next
 gather, and the mixed addition.  Run with the timing build and with the
 normal one (launch time only), at the benched windows (G 29 / Q 29) on the

@@ -1,11 +1,11 @@
-// Latency of the one-launch batched s^-1 (kernels.hip k_ninv_local) on
+// Latency of the one-launch batched s^-1 (ninv_kernels.hip k_ninv_local) on
 // n = 1M random s values, for chains of PER = 2, 4, 8 items per lane
 // (HIP events around each launch, idle GPU).  JSON lines.  (A phase probe
 // with s_memrealtime stamps put the wave inversion at ~43 us of ~90 us at
 // PER = 8, chain up ~20 us, chain down ~15 us: profiles/round3_ubench_ninv.jsonl.)
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -o tools/ubench_ninv tools/ubench_ninv.hip
-#include "../minbft_amd/csrc/kernels.hip"
+#include "../minbft_amd/csrc/ninv_kernels.hip"
 
 #include <algorithm>
 #include <random>
